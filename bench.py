@@ -13,7 +13,19 @@ A third phase times the same workload with the engine's fast RNG mode (cs_config
 byte stream instead of numpy's MT19937, so NOT the reference's deals) and reports it under "rng_philox" -- `value`
 is always the reference-compatible MT19937 stream.
 
+A plain run does only what `value` needs: it builds the envs, picks the trajectory allocation as the library does,
+preconditions, warms up, times the K launches and prints the line (roofline from the timed launches' own HIP events).
+Everything else -- the exchange phase, the Philox phase, the CPU baselines, the write probe, the placement spread, the
+device state and power window -- runs only with --full, where the --no-* / --placement / --gather options choose
+among them.
+
+--dump-outputs DIR writes what the last timed launch left in the trajectory buffers (obs, legal, player, action,
+reward, done: what a caller of VecEnv.rollout receives) as DIR/<name>.npy in float32: all T steps of a fixed, seeded
+sample of the rank's envs (DUMP_BUDGET_BYTES in all). Same arguments, same inputs, same sample: two builds can be
+compared file by file.
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--game leduc-holdem] [--envs N_PER_GPU] [--T STEPS]
+                  [--dump-outputs DIR] [--full]
 """
 import argparse
 import hashlib
@@ -45,6 +57,7 @@ GAMES = {
     # not a BASELINE config; draws/step counted on the oracle (4096 envs x 256 random steps)
     'no-limit-holdem': dict(envs=262144, T=512, draws_per_step=26.3),
 }
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: float32 bytes over all arrays (a dump stays under 64 MB)
 TIMED_TARGET_S = 2.0     # default --steps: enough launches for >= ~2 s of timed region (box variance, SMI sampler)
 
 
@@ -203,6 +216,25 @@ def reference_cpu(game):
                 source='profiles/ref_cpu_baseline.json (%s)' % d['script'], method=d['method'])
 
 
+def dump_outputs(path, traj, rank):
+    """--dump-outputs: the trajectory buffers as <name>.npy (float32), all T steps of a seeded sample of the envs
+    (every env where the whole trajectory fits DUMP_BUDGET_BYTES); rank r > 0 writes <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+    names = ('obs', 'legal', 'player', 'action', 'reward', 'done')
+    T, n = traj['player'].shape
+    per_env = 4 * sum(traj[k][:, 0].numel() for k in names)
+    keep = int(min(n, DUMP_BUDGET_BYTES // per_env))
+    if keep < 1:
+        raise SystemExit('--dump-outputs: one env of %d steps does not fit %d bytes' % (T, DUMP_BUDGET_BYTES))
+    idx = np.sort(np.random.default_rng(20240229).choice(n, size=keep, replace=False)) if keep < n else np.arange(n)
+    sel = torch.from_numpy(idx).to(traj['player'].device)
+    os.makedirs(path, exist_ok=True)
+    for k in names:
+        a = traj[k].index_select(1, sel).cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, k + ('_rank%d' % rank if rank else '') + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -213,15 +245,22 @@ def main():
     ap.add_argument('--envs', type=int, default=0, help='envs per GPU (default: the BASELINE config)')
     ap.add_argument('--T', type=int, default=0, help='fused env steps per launch (default: per game, GAMES)')
     ap.add_argument('--gather', choices=('both', 'rank0', 'all', 'none'), default='both',
-                    help='N>1: trajectory exchange timed after the main loop: every shard into rank 0 ("gather"), '
-                         'all-gathered into every rank (BASELINE config 5, "allgather"), or both (default)')
+                    help='--full, N>1: trajectory exchange timed after the main loop: every shard into rank 0 '
+                         '("gather"), all-gathered into every rank (BASELINE config 5, "allgather"), or both (default)')
     ap.add_argument('--gather-steps', type=int, default=5)
     ap.add_argument('--recv-budget-gb', type=float, default=32.0,
                     help='N>1: receive-buffer budget per GPU of the exchange (GiB); the trajectory moves in T-slices '
                          'that fit it (rlcard_amd/shard.py exchange_traj)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed launches, write the last one\'s trajectory (a seeded sample of the envs, all '
+                         'T steps) as DIR/<name>.npy in float32')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what `value` does not need: the exchange phase (N>1), the Philox phase, the CPU '
+                         'baselines, the write probe, the placement spread, the device state; the options below '
+                         'choose among them')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-philox', dest='philox', action='store_false',
-                    help='skip the CS_RNG_PHILOX phase (reported under "rng_philox")')
+                    help='--full: skip the CS_RNG_PHILOX phase (reported under "rng_philox")')
     ap.add_argument('--no-precondition', dest='precondition', action='store_false',
                     help='time from freshly seeded streams (optimistic: no MT block refills yet)')
     ap.add_argument('--select', type=int, default=None,
@@ -232,15 +271,17 @@ def main():
                     help="new_traj_out's rank: 'rollout' (the library default: the probe's fast class, then one timed "
                          "rollout launch each, env state saved and restored) or 'probe' (the placement probe alone)")
     ap.add_argument('--placement', type=int, default=3,
-                    help='N=1: time a few launches into this many fresh trajectory allocations after the timed region '
-                         '(untimed context under "placement"; 0: off)')
+                    help='--full, N=1: time a few launches into this many fresh trajectory allocations after the timed '
+                         'region (untimed context under "placement"; 0: off)')
     ap.add_argument('--device-state', dest='device_state', action='store_true', default=None,
-                    help='sample the box (HIP attributes + amd-smi, reported under "device"); default: on, except '
-                         'under a profiler (no child processes there)')
+                    help='--full: sample the box (HIP attributes + amd-smi, reported under "device"); default: on, '
+                         'except under a profiler (no child processes there)')
     ap.add_argument('--no-device-state', dest='device_state', action='store_false')
     args = ap.parse_args()
     if args.device_state is None:
         args.device_state = not under_profiler()
+    if not args.full:   # a plain run: the timed launches and their line only
+        args.device_state = False
 
     import torch
     import torch.distributed as dist
@@ -346,18 +387,21 @@ def main():
     kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
     if pw is not None:
         sampler.join(timeout=5)
+    if args.dump_outputs:   # before anything below writes the trajectory buffers again
+        dump_outputs(args.dump_outputs, traj, rank)
 
     # the timed allocation's write ceiling (untimed): the placement probe writes the rollout's trajectory bytes (zeros,
     # the same tensors and order, no game logic), so its rate is what this allocation takes writes at
     write_probe = None
-    if (args.select is None or args.select > 0) and hasattr(_abi.lib(), 'cs_traj_probe'):   # (old A/B builds lack it)
+    # (old A/B builds lack cs_traj_probe)
+    if args.full and (args.select is None or args.select > 0) and hasattr(_abi.lib(), 'cs_traj_probe'):
         wp_ms = sorted(env.probe_traj(traj, T) for _ in range(3))[1]
         wbytes = sum(traj[k].numel() * traj[k].element_size() for k in ('obs', 'legal', 'player', 'action', 'reward', 'done'))
         write_probe = dict(ms=wp_ms, bytes=wbytes, gbs=wbytes / (wp_ms * 1e-3) / 1e9, kernel_over_probe=kernel_ms / wp_ms,
                            note='untimed: cs_traj_probe on the timed trajectory after the timed region (median of 3): '
                                 'the trajectory bytes alone at this allocation\'s write rate')
     placement = None
-    if world == 1 and args.placement > 0:
+    if args.full and world == 1 and args.placement > 0:
         # untimed context for `value` ("the 3.5 / 4.3 ms split"): the same launches into fresh trajectory
         # allocations -- the kernel time follows where the output buffers land in HBM, so a single allocation's
         # time is one draw from this spread
@@ -384,7 +428,7 @@ def main():
         torch.cuda.empty_cache()
 
     gather_info = {}
-    if world > 1 and args.gather != 'none':
+    if args.full and world > 1 and args.gather != 'none':
         # the trajectory exchange: rollout + exchange per step, timed like the main loop
         for mode in (('rank0', 'all') if args.gather == 'both' else (args.gather,)):
             def produce():
@@ -398,7 +442,7 @@ def main():
             torch.cuda.empty_cache()
 
     philox_info = None
-    if args.philox:
+    if args.full and args.philox:
         # the engine's fast RNG mode on the same workload (not the reference's deals): own envs, same buffers
         del env
         penv = ShardedVecEnv(game, N, rank, seed=42, device=local, config={'rng_mode': 'philox'})
@@ -502,7 +546,7 @@ def main():
         line.update(gather_info)
         if philox_info is not None:
             line['rng_philox'] = philox_info
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(game)
             ref = reference_cpu(game)
             if ref is not None:

@@ -33,8 +33,8 @@ def test_traffic_entries_carry_the_digest_and_kernel_time():
 @pytest.mark.gpu
 def test_bench_line_on_the_gpu():
     out = subprocess.run([sys.executable, 'bench.py', '--game', 'leduc-holdem', '--envs', '65536', '--T', '32',
-                          '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-philox', '--no-device-state',
-                          '--placement', '1'],
+                          '--steps', '5', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-philox',
+                          '--no-device-state', '--placement', '1'],
                          cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [x for x in out.stdout.splitlines() if x.startswith('{')]
@@ -54,3 +54,38 @@ def test_bench_line_on_the_gpu():
     trial = sel['trial_ms']
     assert trial is None or (len(trial) == len(sel['probe_ms']) and any(t is not None and t > 0 for t in trial))
     assert len(d['placement']['kernel_ms_per_allocation']) == 2
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full: the timed launches and their line only; --dump-outputs writes the last launch's trajectory
+    (here every env: 300 envs x 8 steps fit the budget) as float32, the arrays VecEnv.rollout returns."""
+    import numpy as np
+    n, T = 300, 8
+    out = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--game', 'leduc-holdem', '--envs', str(n),
+                          '--T', str(T), '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [x for x in out.stdout.splitlines() if x.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['value'] > 0
+    assert d['unit'] == 'env-steps/s' and d['higher_is_better'] is True and d['dtype'] == 'int32'
+    assert d['value'] == pytest.approx(n * T / (d['ms_per_step'] * 1e-3), rel=1e-9)
+    for k in ('cpu_baseline', 'reference_cpu', 'rng_philox', 'device', 'gather', 'allgather'):
+        assert k not in d, k
+    assert 'write_probe' not in d['roofline'] and 'kernel_ms_per_allocation' not in d.get('placement', {})
+    got = {f: np.load(os.path.join(str(tmp_path), f)) for f in sorted(os.listdir(str(tmp_path)))}
+    assert sorted(got) == ['action.npy', 'done.npy', 'legal.npy', 'obs.npy', 'player.npy', 'reward.npy']
+    assert all(a.dtype == np.float32 and a.shape[:2] == (T, n) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    # the same launches through the library in this process: the dump is that caller's last trajectory, bit for bit
+    from rlcard_amd.shard import ShardedVecEnv
+    env = ShardedVecEnv('leduc-holdem', n, 0, seed=42, device=0)
+    env.reset()
+    traj = env.new_traj_out(T)
+    for k in range(bench.precondition_launches('leduc-holdem', T, env) + 1 + 3):
+        env.rollout(T, policy_seed=5, t0=k * T, out=traj)
+    assert got['done.npy'].sum() > 0
+    for k in ('obs', 'legal', 'player', 'action', 'reward', 'done'):
+        assert np.array_equal(got[k + '.npy'], traj[k].cpu().numpy().astype(np.float32)), k

@@ -7,7 +7,7 @@
 # Steps run in order, each under its own time limit; the first failing step ends the call (no retries).
 #   tests[:K_EXPR]            pytest -m gpu [-k K_EXPR]                         -> tests.log
 #   smoke                     __graft_entry__.smoke()                           -> smoke.log
-#   bench:GAME[:ARGS...]      python bench.py --game GAME ARGS (ARGS ','-separated) -> bench_GAME.jsonl
+#   bench:GAME[:ARGS...]      python bench.py --full --game GAME ARGS (ARGS ','-separated) -> bench_GAME.jsonl
 #   counters:GAME:N:T         SQ instruction / wait counters over tools/ab_rollout.py, one PMC pass per group
 #   profile:GAME[:ARGS...]    kernel trace + stats, then FETCH_SIZE and WRITE_SIZE passes over bench.py
 #   ab:GAME:N:T:F1[:F2...]    tools/ab_rollout.py kernel-flag A/B (AB_PLAYERS / AB_WARM from the env)
@@ -48,7 +48,7 @@ for step in "$@"; do
       tail -6 "$O/smoke.log" ;;
     bench)
       g=${a[1]}; extra=$(echo "${a[*]:2}" | tr ',' ' ')
-      run 400 "$O/bench_$g.err" python3 bench.py --game "$g" $extra
+      run 400 "$O/bench_$g.err" python3 bench.py --full --game "$g" $extra
       grep '^{' "$O/bench_$g.err" > "$O/bench_$g.jsonl"; cat "$O/bench_$g.jsonl" ;;
     counters)
       g=${a[1]}; n=${a[2]}; t=${a[3]}; d=$O/cnt_$g; mkdir -p "$d"; i=0
@@ -63,7 +63,7 @@ for step in "$@"; do
       python3 tools/pmc_summary.py "$d" > "$d/summary.txt" 2>&1; cat "$d/summary.txt" ;;
     profile)
       g=${a[1]}; extra=$(echo "${a[*]:2}" | tr ',' ' '); d=$O/prof_$g; mkdir -p "$d"
-      B="bench.py --game $g --no-cpu-baseline --no-philox --no-device-state --placement 0 --gather none --steps ${STEPS:-100} $extra"   # no amd-smi child: under rocprofv3 its env -> python3 hop is an exec after GPU init
+      B="bench.py --game $g --steps ${STEPS:-100} $extra"   # a plain run (no --full): the timed launches only, and no amd-smi child, whose env -> python3 hop under rocprofv3 is an exec after GPU init
       run 300 "$d/bench_kt.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$d/kt" -o kt -- python3 $B
       run 300 "$d/bench_fetch.log" rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$d/fetch" -o fetch -- python3 $B
       run 300 "$d/bench_write.log" rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$d/write" -o write -- python3 $B
