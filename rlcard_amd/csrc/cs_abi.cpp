@@ -16,7 +16,7 @@ std::string table_create(void** dev, Tab* tab);
 
 struct cs_handle {
     cs::Buffers b;
-    cs_game_info info;
+    const cs::GameOps* ops;   // the game type's launchers, cs_game_info and buffer layouts (cs::find_game at cs_create)
     int32_t device;
     bool seeded;
     void* table_dev;     // doudizhu: device action table (one allocation)
@@ -47,25 +47,15 @@ int set_device(const cs_handle* h)
     return e == hipSuccess ? CS_OK : fail_hip(e, "hipSetDevice");
 }
 
-// u32 per env of the MT stream: doudizhu's two word blocks, the others' byte ring (info.rng_period bytes + wbuf)
-// (Blackjack shoes: one 624-word column per env, cs_blackjack_shoe.hip)
-size_t mt_words(const cs_game_info& info)
-{
-    return info.rng_period == 2 * 624 ? (size_t)(2 * 624)
-           : info.rng_period == 624   ? (size_t)624
-                                      : (size_t)cs::RING_ENV_WORDS_HOST;
-}
-
 // the device buffers that hold the envs' state (cs_state_*): pointer and bytes of each, in a fixed order
 int state_parts(const cs_handle* h, void* ptr[5], size_t bytes[5])
 {
     const size_t n = (size_t)h->b.n;
-    const int64_t sb = cs::stage_bytes_per_env(h->b.game, h->info.num_players, h->b.num_decks);
-    ptr[0] = h->b.mt;    bytes[0] = n * mt_words(h->info) * sizeof(uint32_t);
+    ptr[0] = h->b.mt;    bytes[0] = n * (size_t)h->ops->mt_words * sizeof(uint32_t);
     ptr[1] = h->b.ctl;   bytes[1] = n * sizeof(uint32_t);
-    ptr[2] = h->b.state; bytes[2] = n * (size_t)h->info.state_words * sizeof(uint32_t);
+    ptr[2] = h->b.state; bytes[2] = n * (size_t)h->ops->info.state_words * sizeof(uint32_t);
     ptr[3] = h->b.sctl;  bytes[3] = h->b.sctl ? n * sizeof(uint32_t) : 0;
-    ptr[4] = h->b.sbuf;  bytes[4] = h->b.sbuf ? (n + 63) / 64 * 64 * (size_t)sb : 0;
+    ptr[4] = h->b.sbuf;  bytes[4] = h->b.sbuf ? (n + 63) / 64 * 64 * (size_t)h->ops->stage_bytes : 0;
     return 5;
 }
 size_t part_span(size_t bytes) { return (bytes + 255) / 256 * 256; }   // each part 256-B aligned in the buffer
@@ -81,8 +71,9 @@ int cs_game_info_get(int32_t game, const cs_config* cfg, cs_game_info* info)
 {
     if (!info) return fail(CS_E_INVALID, "info is null");
     memset(info, 0, sizeof(*info));
-    int r = cs::game_info(game, cfg, info);
-    if (r != CS_OK) return fail(r, "unsupported game or game config");
+    const cs::GameOps* ops = cs::find_game(game, cfg);
+    if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
+    *info = ops->info;
     return CS_OK;
 }
 
@@ -93,9 +84,9 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     if (num_envs <= 0) return fail(CS_E_INVALID, "num_envs must be positive");
     if (cfg && cfg->rng_mode != CS_RNG_MT19937 && cfg->rng_mode != CS_RNG_PHILOX)
         return fail(CS_E_INVALID, "rng_mode must be CS_RNG_MT19937 or CS_RNG_PHILOX");
-    cs_game_info info;
-    int r = cs_game_info_get(game, cfg, &info);
-    if (r != CS_OK) return r;
+    const cs::GameOps* ops = cs::find_game(game, cfg);
+    if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
+    const cs_game_info& info = ops->info;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) return fail(CS_E_DEVICE, "no HIP device available (the engine needs a GPU)");
@@ -103,7 +94,7 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     cs_handle* h = new (std::nothrow) cs_handle();
     if (!h) return fail(CS_E_INVALID, "out of host memory");
     h->device = device;
-    h->info = info;
+    h->ops = ops;
     h->seeded = false;
     h->b.game = game;
     h->b.n = num_envs;
@@ -118,10 +109,9 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     h->b.rec = cs::StepRecord{nullptr, nullptr, 0u, 0};
     h->b.serial_refill = 0;
     h->b.table = nullptr;
-    if ((r = set_device(h)) != CS_OK) { delete h; return r; }
+    if (int r = set_device(h)) { delete h; return r; }
     const size_t n = (size_t)num_envs;
-    const size_t mtw = mt_words(info);
-    if ((e = hipMalloc((void**)&h->b.mt, n * mtw * sizeof(uint32_t))) != hipSuccess ||
+    if ((e = hipMalloc((void**)&h->b.mt, n * (size_t)ops->mt_words * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc((void**)&h->b.ctl, n * sizeof(uint32_t))) != hipSuccess ||
         (e = hipMalloc((void**)&h->b.state, n * (size_t)info.state_words * sizeof(uint32_t))) != hipSuccess) {
         cs_destroy(h);
@@ -135,11 +125,10 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
         }
         h->b.table = &h->tab;
     }
-    const int64_t sb = cs::stage_bytes_per_env(game, info.num_players, h->b.num_decks);
-    if (sb > 0) {   // rollout staging rows, whole waves (the copy moves 16-B chunks of full rows)
+    if (ops->stage_bytes > 0) {   // rollout staging rows, whole waves (the copy moves 16-B chunks of full rows)
         const size_t rows = (n + 63) / 64 * 64;
         if ((e = hipMalloc((void**)&h->b.sctl, n * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&h->b.sbuf, rows * (size_t)sb)) != hipSuccess) {
+            (e = hipMalloc((void**)&h->b.sbuf, rows * (size_t)ops->stage_bytes)) != hipSuccess) {
             cs_destroy(h);
             return fail_hip(e, "hipMalloc (rollout staging)");
         }
@@ -185,7 +174,7 @@ int cs_seed(cs_handle* h, const uint32_t* keys, const int32_t* key_len, int64_t 
     }
     e = hipMemcpy(dk, keys, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dl, key_len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = cs::launch_seed(h->b, dk, dl, first_env, n, s);
+    if (e == hipSuccess) e = h->ops->seed(h->b, dk, dl, first_env, n, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(dk);
     (void)hipFree(dl);
@@ -201,7 +190,7 @@ int cs_reset(cs_handle* h, const cs_step_out* out, void* stream)
     int r = set_device(h);
     if (r != CS_OK) return r;
     if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = cs::launch_reset(h->b, *out, (hipStream_t)stream);
+    hipError_t e = h->ops->reset(h->b, *out, (hipStream_t)stream);
     if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reset");
 }
@@ -213,7 +202,7 @@ int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* 
     int r = set_device(h);
     if (r != CS_OK) return r;
     if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = cs::launch_step(h->b, actions, *out, (hipStream_t)stream);
+    hipError_t e = h->ops->step(h->b, actions, *out, (hipStream_t)stream);
     if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_step");
 }
@@ -221,11 +210,11 @@ int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* 
 int cs_observe(cs_handle* h, int32_t player, const cs_step_out* out, void* stream)
 {
     if (!h || !out) return fail(CS_E_INVALID, "null argument");
-    if (player < 0 || player >= h->info.num_players) return fail(CS_E_INVALID, "player out of range");
+    if (player < 0 || player >= h->ops->info.num_players) return fail(CS_E_INVALID, "player out of range");
     int r = set_device(h);
     if (r != CS_OK) return r;
     if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = cs::launch_observe(h->b, player, *out, (hipStream_t)stream);
+    hipError_t e = h->ops->observe(h->b, player, *out, (hipStream_t)stream);
     if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_observe");
 }
@@ -264,7 +253,7 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
     if (!h->seeded) return fail(CS_E_STATE, "cs_rollout before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_rollout(h->b, T, policy_seed, t0, env_base, *out, (hipStream_t)stream);
+    hipError_t e = h->ops->rollout(h->b, T, policy_seed, t0, env_base, *out, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_rollout");
 }
 
@@ -286,8 +275,8 @@ int cs_dmc_create(cs_handle* h, int32_t T, int32_t slots, cs_dmc** out)
     if (T <= 0 || slots < 2) return fail(CS_E_INVALID, "cs_dmc_create: T > 0 and slots >= 2");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    const int64_t streams = h->b.n * h->info.num_players, rows = streams * slots * (int64_t)T;
-    const int64_t O = h->info.obs_dim, F = h->info.action_feature_dim;
+    const int64_t streams = h->b.n * h->ops->info.num_players, rows = streams * slots * (int64_t)T;
+    const int64_t O = h->ops->info.obs_dim, F = h->ops->info.action_feature_dim;
     auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
     const int64_t o_st = 0, o_act = o_st + al(rows * O), o_tgt = o_act + al(rows * F), o_ret = o_tgt + al(rows * 4),
                   o_dne = o_ret + al(rows * 4), o_ctr = o_dne + al(rows), o_gs = o_ctr + al(streams * 8),
@@ -349,13 +338,14 @@ int cs_dmc_gather(cs_dmc* d, int32_t player, const int64_t* chunks, int64_t coun
                   void* stream)
 {
     if (!d || !out || (count > 0 && !chunks)) return fail(CS_E_INVALID, "null argument");
-    if (player < 0 || player >= d->h->info.num_players) return fail(CS_E_INVALID, "player out of range");
+    if (player < 0 || player >= d->h->ops->info.num_players) return fail(CS_E_INVALID, "player out of range");
     if (count < 0 || count > 0x7FFFFFFF) return fail(CS_E_INVALID, "count out of range");
     if (count == 0) return CS_OK;
     int r = set_device(d->h);
     if (r != CS_OK) return r;
-    const int32_t sd = d->h->b.game == CS_GAME_DOUDIZHU && player == 0 ? cs::ddz::OBS_LANDLORD : d->h->info.obs_dim;
-    hipError_t e = cs::launch_dmc_gather(d->r, sd, d->h->info.obs_dim, chunks, count, *out, (hipStream_t)stream);
+    const int32_t od = d->h->ops->info.obs_dim;
+    const int32_t sd = d->h->b.game == CS_GAME_DOUDIZHU && player == 0 ? cs::ddz::OBS_LANDLORD : od;
+    hipError_t e = cs::launch_dmc_gather(d->r, sd, od, chunks, count, *out, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_gather");
 }
 
@@ -376,7 +366,7 @@ int cs_dmc_layer1(cs_handle* h, const float* X, const int32_t* state_of, const i
     if (E == 0) return CS_OK;
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_dmc_layer1(X, state_of, ids, E, H, W_act, b1, h->info.action_feature_dim, h->b, h1,
+    hipError_t e = cs::launch_dmc_layer1(X, state_of, ids, E, H, W_act, b1, h->ops->info.action_feature_dim, h->b, h1,
                                          (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_layer1");
 }
@@ -399,9 +389,9 @@ int cs_traj_probe(cs_handle* h, int32_t T, const cs_traj_out* out, void* stream)
         if (((uintptr_t)p & 15u) != 0) return fail(CS_E_INVALID, "trajectory tensors must be 16-byte aligned");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    const int32_t epw = h->info.envs_per_wave;   // the game's rollout kernel's (G::EPW, filled by game_info)
-    hipError_t e = cs::launch_traj_probe(h->b, T, *out, h->info.obs_dim, h->info.legal_bytes, h->info.action_bytes, epw,
-                                         (hipStream_t)stream);
+    const cs_game_info& info = h->ops->info;   // envs_per_wave: the game's rollout kernel's (G::EPW)
+    hipError_t e = cs::launch_traj_probe(h->b, T, *out, info.obs_dim, info.legal_bytes, info.action_bytes,
+                                         info.envs_per_wave, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_traj_probe");
 }
 
@@ -458,8 +448,8 @@ int cs_legal_lists(cs_handle* h, const void* legal, int64_t rows, int32_t* count
     if (rows <= 0 || rows > ((int64_t)1 << 31) - 1) return fail(CS_E_INVALID, "rows out of range");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_legal_lists(h->b, h->info.legal_bytes, (const uint8_t*)legal, rows, counts, offsets, ids,
-                                          &h->scan_tmp, &h->scan_bytes, (hipStream_t)stream);
+    hipError_t e = cs::launch_legal_lists(h->b, h->ops->info.legal_bytes, (const uint8_t*)legal, rows, counts, offsets,
+                                          ids, &h->scan_tmp, &h->scan_bytes, (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_legal_lists");
 }
 
@@ -469,21 +459,22 @@ int cs_action_features(cs_handle* h, const int32_t* ids, int64_t count, void* fe
     if (count <= 0) return fail(CS_E_INVALID, "count must be positive");
     int r = set_device(h);
     if (r != CS_OK) return r;
+    hipStream_t s = (hipStream_t)stream;
     hipError_t e = h->b.game == CS_GAME_DOUDIZHU
-                       ? cs::ddz::launch_features(h->b, ids, count, (uint8_t*)features, (hipStream_t)stream)
-                       : cs::launch_onehot(ids, count, h->info.num_actions, (uint8_t*)features, (hipStream_t)stream);
+                       ? cs::ddz::launch_features(h->b, ids, count, (uint8_t*)features, s)
+                       : cs::launch_onehot(ids, count, h->ops->info.num_actions, (uint8_t*)features, s);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_action_features");
 }
 
 int cs_get_env_state(cs_handle* h, int64_t env, uint32_t* host_words, int32_t nwords)
 {
     if (!h || !host_words) return fail(CS_E_INVALID, "null argument");
-    if (env < 0 || env >= h->b.n || nwords < h->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
+    if (env < 0 || env >= h->b.n || nwords < h->ops->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
     int r = set_device(h);
     if (r != CS_OK) return r;
     hipError_t e = hipDeviceSynchronize();
-    const int sw = h->info.state_words;
-    if (cs::state_env_major(h->b.game)) {
+    const int sw = h->ops->info.state_words;
+    if (h->ops->env_major) {
         if (e == hipSuccess)
             e = hipMemcpy(host_words, h->b.state + (size_t)env * sw, sizeof(uint32_t) * sw, hipMemcpyDeviceToHost);
     } else {
@@ -498,22 +489,23 @@ int cs_copy_env_state(cs_handle* h, int64_t env, uint32_t* dst, void* stream)
 {
     if (!h || !dst) return fail(CS_E_INVALID, "null argument");
     if (env < 0 || env >= h->b.n) return fail(CS_E_INVALID, "bad env");
-    if (h->info.state_words > 64) return fail(CS_E_UNSUPPORTED, "state too large for cs_copy_env_state");
+    if (h->ops->info.state_words > 64) return fail(CS_E_UNSUPPORTED, "state too large for cs_copy_env_state");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_copy_state(h->b, env, h->info.state_words, dst, (hipStream_t)stream);
+    hipError_t e = cs::launch_copy_state(h->b, env, h->ops->info.state_words, h->ops->env_major ? 1 : 0, dst,
+                                         (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_copy_env_state");
 }
 
 int cs_set_env_state(cs_handle* h, int64_t env, const uint32_t* host_words, int32_t nwords)
 {
     if (!h || !host_words) return fail(CS_E_INVALID, "null argument");
-    if (env < 0 || env >= h->b.n || nwords < h->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
+    if (env < 0 || env >= h->b.n || nwords < h->ops->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
     int r = set_device(h);
     if (r != CS_OK) return r;
     hipError_t e = hipDeviceSynchronize();
-    const int sw = h->info.state_words;
-    if (cs::state_env_major(h->b.game)) {
+    const int sw = h->ops->info.state_words;
+    if (h->ops->env_major) {
         if (e == hipSuccess)
             e = hipMemcpy(h->b.state + (size_t)env * sw, host_words, sizeof(uint32_t) * sw, hipMemcpyHostToDevice);
     } else {
@@ -524,20 +516,10 @@ int cs_set_env_state(cs_handle* h, int64_t env, const uint32_t* host_words, int3
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_set_env_state");
 }
 
-// the env's mt footprint (u32) and layout, as cs_create allocated it
-static void rng_layout(const cs_handle* h, int32_t* mtw, int32_t* column)
-{
-    const int32_t p = h->info.rng_period;
-    *mtw = p == 2 * 624 ? 2 * 624 : p == 624 ? 624 : (int32_t)cs::RING_ENV_WORDS_HOST;
-    *column = p == 624 ? 1 : 0;   // Blackjack shoes: word k of env e at mt[k * n + e]
-}
-
 int cs_env_rng_words(cs_handle* h, int32_t* words)
 {
     if (!h || !words) return fail(CS_E_INVALID, "null argument");
-    int32_t mtw, column;
-    rng_layout(h, &mtw, &column);
-    *words = 1 + mtw;
+    *words = 1 + h->ops->mt_words;
     return CS_OK;
 }
 
@@ -547,10 +529,9 @@ static int rng_copy(cs_handle* h, int64_t env, uint32_t* buf, int32_t load, void
     if (env < 0 || env >= h->b.n) return fail(CS_E_INVALID, "bad env");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    int32_t mtw, column;
-    rng_layout(h, &mtw, &column);
     const uint32_t clear = h->b.sbuf ? (1u << 17) : 0u;   // restored streams restage from the ring
-    hipError_t e = cs::launch_rng_copy(h->b, env, mtw, column, clear, buf, load, (hipStream_t)stream);
+    hipError_t e = cs::launch_rng_copy(h->b, env, h->ops->mt_words, h->ops->mt_columns ? 1 : 0, clear, buf, load,
+                                       (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, what);
 }
 

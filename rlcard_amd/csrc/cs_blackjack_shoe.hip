@@ -384,62 +384,68 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(uint32_t* mt, uint32_t* ctl, 
 
 dim3 grid_of(int64_t n) { return dim3((unsigned)((n + BLOCK - 1) / BLOCK)); }
 
+static hipError_t launch_seed(const Buffers& b, const uint32_t* keys, const int32_t* klen, int64_t first,
+                              int64_t count, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_seed, grid_of(count), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, keys, klen, first, count);
+    return hipGetLastError();
+}
+static hipError_t launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_reset, grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, o, params_of(b), b.rec);
+    return hipGetLastError();
+}
+static hipError_t launch_step(const Buffers& b, const int32_t* a, const cs_step_out& o, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_step, grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, a, o, params_of(b), b.rec);
+    return hipGetLastError();
+}
+static hipError_t launch_observe(const Buffers& b, int32_t p, const cs_step_out& o, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_observe, grid_of(b.n), dim3(BLOCK), 0, s, b.state, b.n, p, o, params_of(b), b.rec);
+    return hipGetLastError();
+}
+static hipError_t launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
+                                 const cs_traj_out& o, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_rollout, grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, T, seed, t0, env_base, o,
+                       params_of(b));
+    return hipGetLastError();
+}
+
+// one kernel set serves every table; the descriptors differ in info.num_players only
+struct Tables {
+    GameOps ops[MAXP];
+    Tables()
+    {
+        for (int np = 1; np <= MAXP; np++) {
+            cs_game_info info{};
+            info.obs_dim = 2;
+            info.num_actions = 2;
+            info.num_players = np;
+            info.legal_bytes = 1;
+            info.action_bytes = 1;
+            info.state_words = WORDS;
+            info.action_feature_dim = 2;
+            info.rng_period = MT_N;   // position = words consumed of the current 624-word block
+            info.game_words = WORDS;
+            info.envs_per_wave = WAVE;   // k_rollout: one lane per env
+            // no rollout staging; the env's 624 MT words are a column of the mt buffer
+            ops[np - 1] = GameOps{launch_seed, launch_reset, launch_step, launch_observe, launch_rollout,
+                                  info, 0, MT_N, true, false};
+        }
+    }
+};
+
 }  // namespace bjs
 
-bool is_blackjack_shoe(const Buffers& b)
+const GameOps* find_blackjack_shoe(int32_t np, int32_t nd, int32_t rng_mode)
 {
-    return b.game == CS_GAME_BLACKJACK && (b.num_decks >= 2 || b.num_players > 4);
-}
-
-int bjs_game_info(const cs_config* cfg, cs_game_info* info)
-{
-    const int np = cfg && cfg->num_players > 0 ? cfg->num_players : 1;
-    const int nd = cfg && cfg->num_decks >= 0 ? cfg->num_decks : 1;
-    if (np > bjs::MAXP || nd > 8) return CS_E_UNSUPPORTED;
-    if (cfg && cfg->rng_mode == CS_RNG_PHILOX) return CS_E_UNSUPPORTED;   // the Philox stream is bytes (cs_ring.h)
-    info->obs_dim = 2;
-    info->num_actions = 2;
-    info->num_players = np;
-    info->legal_bytes = 1;
-    info->action_bytes = 1;
-    info->state_words = bjs::WORDS;
-    info->action_feature_dim = 2;
-    info->rng_period = MT_N;   // position = words consumed of the current 624-word block
-    info->game_words = bjs::WORDS;
-    info->envs_per_wave = WAVE;   // k_rollout: one lane per env
-    return CS_OK;
-}
-
-hipError_t bjs_launch_seed(const Buffers& b, const uint32_t* keys, const int32_t* klen, int64_t first, int64_t count,
-                           hipStream_t s)
-{
-    hipLaunchKernelGGL(bjs::k_seed, bjs::grid_of(count), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, keys, klen,
-                       first, count);
-    return hipGetLastError();
-}
-hipError_t bjs_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s)
-{
-    hipLaunchKernelGGL(bjs::k_reset, bjs::grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, o, params_of(b),
-                       b.rec);
-    return hipGetLastError();
-}
-hipError_t bjs_launch_step(const Buffers& b, const int32_t* a, const cs_step_out& o, hipStream_t s)
-{
-    hipLaunchKernelGGL(bjs::k_step, bjs::grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, a, o,
-                       params_of(b), b.rec);
-    return hipGetLastError();
-}
-hipError_t bjs_launch_observe(const Buffers& b, int32_t p, const cs_step_out& o, hipStream_t s)
-{
-    hipLaunchKernelGGL(bjs::k_observe, bjs::grid_of(b.n), dim3(BLOCK), 0, s, b.state, b.n, p, o, params_of(b), b.rec);
-    return hipGetLastError();
-}
-hipError_t bjs_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                              const cs_traj_out& o, hipStream_t s)
-{
-    hipLaunchKernelGGL(bjs::k_rollout, bjs::grid_of(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, T, seed, t0,
-                       env_base, o, params_of(b));
-    return hipGetLastError();
+    static const bjs::Tables tables;
+    if (np < 1 || np > bjs::MAXP || nd > 8) return nullptr;
+    if (rng_mode == CS_RNG_PHILOX) return nullptr;   // the Philox stream is bytes (cs_ring.h)
+    return &tables.ops[np - 1];
 }
 
 }  // namespace cs
+

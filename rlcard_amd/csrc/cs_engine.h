@@ -1,4 +1,5 @@
-// cs_engine.h -- internal interface between the C ABI (cs_abi.cpp) and the kernels (cs_kernels.hip).
+// cs_engine.h -- internal interface between the C ABI (cs_abi.cpp) and the kernels: the device buffers of a handle, the
+// per-game-type launch table (GameOps, find_game) and the launchers of the game-independent kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,74 +55,33 @@ struct DmcRing {
     uint32_t* flag;               // bit 0: rows dropped (ring full)
 };
 
-int game_info(int32_t game, const cs_config* cfg, cs_game_info* info);
-int64_t stage_bytes_per_env(int32_t game, int32_t num_players, int32_t num_decks);
-inline bool state_env_major(int32_t game) { return game == CS_GAME_DOUDIZHU; }
-
-hipError_t launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
+// One concrete game type -- a Game class of the skeleton (cs_skeleton.h ops_of<G>), the Blackjack shoe or DouDizhu: its
+// five launchers and the facts the ABI layer needs about it. cs_create looks it up once (find_game) and the handle
+// keeps the pointer: the allocation and every launch follow the same descriptor.
+struct GameOps {
+    hipError_t (*seed)(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
                        int64_t count, hipStream_t s);
-hipError_t launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
+    hipError_t (*reset)(const Buffers& b, const cs_step_out& o, hipStream_t s);
+    hipError_t (*step)(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
+    hipError_t (*observe)(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
+    hipError_t (*rollout)(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
                           const cs_traj_out& o, hipStream_t s);
+    cs_game_info info;      // what cs_game_info_get reports
+    int32_t stage_bytes;    // rollout MT staging row per env (Buffers::sbuf), 0: none
+    int32_t mt_words;       // u32 per env in Buffers::mt
+    bool mt_columns;        // word k of env e at mt[k * n + e] (the shoe) instead of mt[e * mt_words + k]
+    bool env_major;         // state is [n][state_words] (DouDizhu) instead of [state_words][n]
+};
 
-// cs_holdem_n.hip: 3..6-player hold'em (Leduc 3..5), used when Buffers::num_players > 2
-bool np_supported(int32_t game, int32_t num_players);
-int np_game_info(int32_t game, int32_t num_players, cs_game_info* info);
-int64_t np_stage_bytes(int32_t game, int32_t num_players);
-hipError_t np_launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
-                          int64_t count, hipStream_t s);
-hipError_t np_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t np_launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t np_launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t np_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                             const cs_traj_out& o, hipStream_t s);
-// cs_holdem_n10.hip: the same for 7..10 players (Limit / No-limit)
-int np10_game_info(int32_t game, int32_t num_players, cs_game_info* info);
-int64_t np10_stage_bytes(int32_t game, int32_t num_players);
-hipError_t np10_launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
-                            int64_t count, hipStream_t s);
-hipError_t np10_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t np10_launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t np10_launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t np10_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                               const cs_traj_out& o, hipStream_t s);
-// cs_holdem_n16.hip: the same for 11..16 players
-int np16_game_info(int32_t game, int32_t num_players, cs_game_info* info);
-int64_t np16_stage_bytes(int32_t game, int32_t num_players);
-hipError_t np16_launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
-                            int64_t count, hipStream_t s);
-hipError_t np16_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t np16_launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t np16_launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t np16_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                               const cs_traj_out& o, hipStream_t s);
-// cs_holdem_n22.hip: the same for 17..22 players
-int np22_game_info(int32_t game, int32_t num_players, cs_game_info* info);
-int64_t np22_stage_bytes(int32_t game, int32_t num_players);
-hipError_t np22_launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
-                            int64_t count, hipStream_t s);
-hipError_t np22_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t np22_launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t np22_launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t np22_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                               const cs_traj_out& o, hipStream_t s);
-// cs_blackjack_shoe.hip: Blackjack with 2..8-deck shoes or 5..7 players (word-stream RNG, materialised shoe)
-bool is_blackjack_shoe(const Buffers& b);
-int bjs_game_info(const cs_config* cfg, cs_game_info* info);
-hipError_t bjs_launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
-                           int64_t count, hipStream_t s);
-hipError_t bjs_launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
-hipError_t bjs_launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
-hipError_t bjs_launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);
-hipError_t bjs_launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                              const cs_traj_out& o, hipStream_t s);
-
-inline bool is_holdem_n(const Buffers& b)
-{
-    return (b.game == CS_GAME_LEDUC || b.game == CS_GAME_LIMIT || b.game == CS_GAME_NOLIMIT) && b.num_players > 2;
-}
+// The type that serves `cfg` (null: the game's defaults), or null where the engine has none (cs_kernels.hip). The
+// other units each export one function, the finder of the types they instantiate (null for any other):
+const GameOps* find_game(int32_t game, const cs_config* cfg);
+const GameOps* find_holdem_n(int32_t game, int32_t num_players);     // cs_holdem_n.hip: 3..6 (Leduc 3..5) + the next 3
+const GameOps* find_holdem_n10(int32_t game, int32_t num_players);   // cs_holdem_n10.hip: Limit / No-limit 7..10
+const GameOps* find_holdem_n16(int32_t game, int32_t num_players);   // cs_holdem_n16.hip: 11..16
+const GameOps* find_holdem_n22(int32_t game, int32_t num_players);   // cs_holdem_n22.hip: 17..22
+// cs_blackjack_shoe.hip: Blackjack up to 7 players and 8 decks (word-stream RNG, materialised shoe; MT19937 only)
+const GameOps* find_blackjack_shoe(int32_t num_players, int32_t num_decks, int32_t rng_mode);
 
 // cs_dmc.hip
 hipError_t launch_dmc_fill(const Buffers& b, const DmcRing& d, int32_t T, const cs_traj_out& tr, int64_t* ready,
@@ -158,7 +118,8 @@ hipError_t launch_transitions(const Buffers& b, int32_t T, const cs_traj_out& tr
 hipError_t launch_legal_lists(const Buffers& b, int32_t lb, const uint8_t* legal, int64_t rows, int32_t* counts,
                               int64_t* offsets, int32_t* ids, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_onehot(const int32_t* ids, int64_t count, int32_t na, uint8_t* out, hipStream_t s);
-hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, uint32_t* dst, hipStream_t s);
+hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, int32_t env_major, uint32_t* dst,
+                             hipStream_t s);
 hipError_t launch_rng_copy(const Buffers& b, int64_t env, int32_t mtw, int32_t column, uint32_t clear_mask,
                            uint32_t* buf, int32_t load, hipStream_t s);   // cs_traj.hip
 hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, hipStream_t s);   // cs_kernels.hip

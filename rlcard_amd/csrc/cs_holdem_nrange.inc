@@ -1,85 +1,27 @@
 // cs_holdem_nrange.inc -- one translation unit's worth of the lockstep skeleton (cs_skeleton.h) instantiated for
-// Limit / No-limit hold'em with CS_NP_LO..CS_NP_HI players (cs_holdem_n.h), behind the launchers CS_NP_NAME(game_info)
-// .. CS_NP_NAME(launch_rollout) that cs_holdem_n.hip calls for cs_config.num_players > 6. Included by
-// cs_holdem_n10.hip (7..10), cs_holdem_n16.hip (11..16) and cs_holdem_n22.hip (17..22): the big player counts are
-// split over three units so that they compile in parallel.
+// Limit / No-limit hold'em with CS_NP_LO..CS_NP_HI players (cs_holdem_n.h), behind the unit's one export: the finder
+// CS_NP_NAME, which cs_holdem_n.hip's find_holdem_n asks for more than 6 players. Included by cs_holdem_n10.hip
+// (7..10), cs_holdem_n16.hip (11..16) and cs_holdem_n22.hip (17..22): the big player counts are split over three
+// units so that they compile in parallel.
 #include "cs_skeleton.h"
 #include "cs_holdem_n.h"
 
 namespace cs {
-namespace {
 
-template <class G>
-struct Tag {
-    using type = G;
-};
-
-// f(Tag<LimitN<np>>) / f(Tag<NolimitN<np>>) for np in [P, HI]; `fail` otherwise
-template <int P, int HI, class F, class R>
-R np_range(int32_t game, int32_t np, const F& f, R fail)
+// LimitN<np> / NolimitN<np> for np in [P, HI]; null otherwise
+template <int P, int HI>
+static const GameOps* np_range(int32_t game, int32_t np)
 {
     if constexpr (P > HI) {
-        return fail;
+        return nullptr;
     } else {
-        if (np == P) {
-            if (game == CS_GAME_LIMIT) return f(Tag<LimitN<P>>{});
-            if (game == CS_GAME_NOLIMIT) return f(Tag<NolimitN<P>>{});
-            return fail;
-        }
-        return np_range<P + 1, HI>(game, np, f, fail);
+        if (np != P) return np_range<P + 1, HI>(game, np);
+        if (game == CS_GAME_LIMIT) return ops_of<LimitN<P>>();
+        if (game == CS_GAME_NOLIMIT) return ops_of<NolimitN<P>>();
+        return nullptr;
     }
 }
 
-template <class F, class R>
-R dispatch(int32_t game, int32_t np, const F& f, R fail)
-{
-    return np_range<CS_NP_LO, CS_NP_HI>(game, np, f, fail);
-}
-
-}  // namespace
-
-#define CS_G_ typename decltype(t)::type
-
-int CS_NP_NAME(game_info)(int32_t game, int32_t np, cs_game_info* info)
-{
-    return dispatch(game, np, [&](auto t) { return (fill_info<CS_G_>(info), (int)CS_OK); }, (int)CS_E_UNSUPPORTED);
-}
-
-int64_t CS_NP_NAME(stage_bytes)(int32_t game, int32_t np)
-{
-    return dispatch(game, np, [&](auto t) { return (int64_t)stage_bytes_of<CS_G_>(); }, (int64_t)0);
-}
-
-hipError_t CS_NP_NAME(launch_seed)(const Buffers& b, const uint32_t* keys, const int32_t* klen, int64_t first,
-                                   int64_t count, hipStream_t s)
-{
-    return dispatch(b.game, b.num_players, [&](auto t) { return seed_g<CS_G_>(b, keys, klen, first, count, s); },
-                    hipErrorInvalidValue);
-}
-
-hipError_t CS_NP_NAME(launch_reset)(const Buffers& b, const cs_step_out& o, hipStream_t s)
-{
-    return dispatch(b.game, b.num_players, [&](auto t) { return reset_g<CS_G_>(b, o, s); }, hipErrorInvalidValue);
-}
-
-hipError_t CS_NP_NAME(launch_step)(const Buffers& b, const int32_t* a, const cs_step_out& o, hipStream_t s)
-{
-    return dispatch(b.game, b.num_players, [&](auto t) { return step_g<CS_G_>(b, a, o, s); }, hipErrorInvalidValue);
-}
-
-hipError_t CS_NP_NAME(launch_observe)(const Buffers& b, int32_t p, const cs_step_out& o, hipStream_t s)
-{
-    return dispatch(b.game, b.num_players, [&](auto t) { return observe_g<CS_G_>(b, p, o, s); },
-                    hipErrorInvalidValue);
-}
-
-hipError_t CS_NP_NAME(launch_rollout)(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                                      const cs_traj_out& o, hipStream_t s)
-{
-    return dispatch(b.game, b.num_players,
-                    [&](auto t) { return rollout_g<CS_G_>(b, T, seed, t0, env_base, o, s); }, hipErrorInvalidValue);
-}
-
-#undef CS_G_
+const GameOps* CS_NP_NAME(int32_t game, int32_t np) { return np_range<CS_NP_LO, CS_NP_HI>(game, np); }
 
 }  // namespace cs

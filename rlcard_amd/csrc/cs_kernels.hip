@@ -1,7 +1,9 @@
 // cs_kernels.hip -- lockstep env kernels for gfx950 (one lane = one env, one wave = 64 consecutive envs).
 //
 // The kernel skeleton (cs_skeleton.h) instantiated for the heads-up hold'em games, Blackjack and DouDizhu's seeding;
-// 3..6-player hold'em is instantiated in cs_holdem_n.hip. game_info / dispatch for the C ABI (cs_abi.cpp).
+// 3..22-player hold'em is instantiated in cs_holdem_n*.hip, the Blackjack shoe in cs_blackjack_shoe.hip. find_game
+// maps a game id and cs_config to the launch table entry (cs_engine.h GameOps) of its type; this is the one place
+// that decides it, and cs_abi.cpp asks once per handle.
 #include "cs_skeleton.h"
 #include "cs_leduc.h"
 #include "cs_limit.h"
@@ -11,83 +13,61 @@
 
 namespace cs {
 
-int64_t stage_bytes_per_env(int32_t game, int32_t num_players, int32_t num_decks)
+// DouDizhu: its own kernels (cs_doudizhu.hip: a wave per env, env-major state, two 624-word MT blocks per env) behind
+// the skeleton's k_seed
+static const GameOps* ddz_ops()
 {
-    if (game == CS_GAME_BLACKJACK && (num_decks >= 2 || num_players > 4)) return 0;   // cs_blackjack_shoe.hip
-    switch (game) {
-    case CS_GAME_LEDUC: return num_players > 2 ? np_stage_bytes(game, num_players) : stage_bytes_of<Leduc>();
-    case CS_GAME_LIMIT: return num_players > 2 ? np_stage_bytes(game, num_players) : stage_bytes_of<Limit>();
-    case CS_GAME_BLACKJACK: return num_players <= 1 ? stage_bytes_of<Blackjack<1>>() : stage_bytes_of<Blackjack<4>>();
-    case CS_GAME_NOLIMIT: return num_players > 2 ? np_stage_bytes(game, num_players) : stage_bytes_of<Nolimit>();
-    default: return 0;
-    }
+    static const GameOps ops = [] {
+        cs_game_info info{};
+        info.obs_dim = ddz::OBS;
+        info.num_actions = ddz::NA;
+        info.num_players = ddz::P;
+        info.legal_bytes = ddz::LB;
+        info.action_bytes = 2;
+        info.state_words = ddz::WORDS;
+        info.action_feature_dim = 54;
+        info.rng_period = 2 * 624;
+        info.game_words = ddz::WORDS;
+        info.envs_per_wave = 2;   // k_rollout2: one env per half-wave
+        return GameOps{seed_g<ddz::SeedView>, ddz::launch_reset, ddz::launch_step, ddz::launch_observe,
+                       ddz::launch_rollout, info, 0, 2 * 624, false, true};
+    }();
+    return &ops;
 }
 
-int game_info(int32_t game, const cs_config* cfg, cs_game_info* info)
+const GameOps* find_game(int32_t game, const cs_config* cfg)
 {
+    const int32_t np = cfg ? cfg->num_players : 0;   // <= 0: the game's default
     switch (game) {
     case CS_GAME_LEDUC:
-        if (cfg && cfg->num_players > 2) return np_game_info(game, cfg->num_players, info);
-        if (cfg && cfg->num_players != 0 && cfg->num_players != 2) return CS_E_UNSUPPORTED;
-        fill_info<Leduc>(info);
-        return CS_OK;
     case CS_GAME_LIMIT:
-        if (cfg && cfg->num_players > 2) return np_game_info(game, cfg->num_players, info);
-        if (cfg && cfg->num_players != 0 && cfg->num_players != 2) return CS_E_UNSUPPORTED;
-        fill_info<Limit>(info);
-        return CS_OK;
+        if (np > 2) return find_holdem_n(game, np);
+        if (np != 0 && np != 2) return nullptr;
+        return game == CS_GAME_LEDUC ? ops_of<Leduc>() : ops_of<Limit>();
     case CS_GAME_BLACKJACK: {
-        const int np = (cfg && cfg->num_players > 0) ? cfg->num_players : 1;
-        const int nd = (cfg && cfg->num_decks >= 0) ? cfg->num_decks : 1;
-        if (np > 4 || nd > 1) return bjs_game_info(cfg, info);   // shoes and big tables: cs_blackjack_shoe.hip
-        if (np == 1) fill_info<Blackjack<1>>(info);
-        else if (np == 2) fill_info<Blackjack<2>>(info);
-        else if (np == 3) fill_info<Blackjack<3>>(info);
-        else fill_info<Blackjack<4>>(info);
-        return CS_OK;
+        const int32_t p = np > 0 ? np : 1, nd = (cfg && cfg->num_decks >= 0) ? cfg->num_decks : 1;
+        // the byte-ring kernel (cs_blackjack.h) covers one deck and at most 4 players; the rest (which only a cfg
+        // asks for) are shoes
+        if (p > 4 || nd > 1) return find_blackjack_shoe(p, nd, cfg->rng_mode);
+        switch (p) {
+        case 1: return ops_of<Blackjack<1>>();
+        case 2: return ops_of<Blackjack<2>>();
+        case 3: return ops_of<Blackjack<3>>();
+        default: return ops_of<Blackjack<4>>();
+        }
     }
     case CS_GAME_NOLIMIT: {
-        const int np = (cfg && cfg->num_players > 0) ? cfg->num_players : 2;
+        const int32_t p = np > 0 ? np : 2;
         if (cfg && (cfg->chips_for_each < 0 || cfg->chips_for_each > 255 || cfg->dealer_plus1 < 0 ||
-                    cfg->dealer_plus1 > np))
-            return CS_E_UNSUPPORTED;
-        if (np > 2) return np_game_info(game, np, info);
-        if (np != 2) return CS_E_UNSUPPORTED;
-        fill_info<Nolimit>(info);
-        return CS_OK;
+                    cfg->dealer_plus1 > p))
+            return nullptr;
+        if (p > 2) return find_holdem_n(game, p);
+        return p == 2 ? ops_of<Nolimit>() : nullptr;
     }
-    case CS_GAME_DOUDIZHU:
-        if (cfg && cfg->num_players != 0 && cfg->num_players != ddz::P) return CS_E_UNSUPPORTED;
-        info->obs_dim = ddz::OBS;
-        info->num_actions = ddz::NA;
-        info->num_players = ddz::P;
-        info->legal_bytes = ddz::LB;
-        info->action_bytes = 2;
-        info->state_words = ddz::WORDS;
-        info->action_feature_dim = 54;
-        info->rng_period = 2 * 624;
-        info->game_words = ddz::WORDS;
-        info->envs_per_wave = 2;   // k_rollout2: one env per half-wave
-        return CS_OK;
-    default:
-        return CS_E_UNSUPPORTED;
+    case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
+    default: return nullptr;
     }
 }
-
-#define CS_DISPATCH(game, CALL)                                  \
-    switch (game) {                                              \
-    case CS_GAME_LEDUC: return CALL(Leduc);                      \
-    case CS_GAME_LIMIT: return CALL(Limit);                      \
-    case CS_GAME_NOLIMIT: return CALL(Nolimit);                  \
-    case CS_GAME_BLACKJACK:                                      \
-        switch (b.num_players) {                                 \
-        case 1: return CALL(Blackjack<1>);                       \
-        case 2: return CALL(Blackjack<2>);                       \
-        case 3: return CALL(Blackjack<3>);                       \
-        default: return CALL(Blackjack<4>);                      \
-        }                                                        \
-    default: return hipErrorInvalidValue;                        \
-    }
 
 // Test hook (cs_debug_holdem_rank7): the showdown evaluator of the hold'em kernels (tally_card + holdem_rank7, the
 // functions holdem_showdown and Limit's game end call) on arbitrary 7-card hands, one thread per hand
@@ -105,54 +85,6 @@ hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, 
 {
     hipLaunchKernelGGL(k_debug_rank7, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cards, n, values);
     return hipGetLastError();
-}
-
-hipError_t launch_seed(const Buffers& b, const uint32_t* keys, const int32_t* klen, int64_t first, int64_t count,
-                       hipStream_t s)
-{
-#define C_(G) seed_g<G>(b, keys, klen, first, count, s)
-    if (b.game == CS_GAME_DOUDIZHU) return C_(ddz::SeedView);
-    if (is_blackjack_shoe(b)) return bjs_launch_seed(b, keys, klen, first, count, s);
-    if (is_holdem_n(b)) return np_launch_seed(b, keys, klen, first, count, s);
-    CS_DISPATCH(b.game, C_)
-#undef C_
-}
-hipError_t launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s)
-{
-#define C_(G) reset_g<G>(b, o, s)
-    if (b.game == CS_GAME_DOUDIZHU) return ddz::launch_reset(b, o, s);
-    if (is_blackjack_shoe(b)) return bjs_launch_reset(b, o, s);
-    if (is_holdem_n(b)) return np_launch_reset(b, o, s);
-    CS_DISPATCH(b.game, C_)
-#undef C_
-}
-hipError_t launch_step(const Buffers& b, const int32_t* a, const cs_step_out& o, hipStream_t s)
-{
-#define C_(G) step_g<G>(b, a, o, s)
-    if (b.game == CS_GAME_DOUDIZHU) return ddz::launch_step(b, a, o, s);
-    if (is_blackjack_shoe(b)) return bjs_launch_step(b, a, o, s);
-    if (is_holdem_n(b)) return np_launch_step(b, a, o, s);
-    CS_DISPATCH(b.game, C_)
-#undef C_
-}
-hipError_t launch_observe(const Buffers& b, int32_t p, const cs_step_out& o, hipStream_t s)
-{
-#define C_(G) observe_g<G>(b, p, o, s)
-    if (b.game == CS_GAME_DOUDIZHU) return ddz::launch_observe(b, p, o, s);
-    if (is_blackjack_shoe(b)) return bjs_launch_observe(b, p, o, s);
-    if (is_holdem_n(b)) return np_launch_observe(b, p, o, s);
-    CS_DISPATCH(b.game, C_)
-#undef C_
-}
-hipError_t launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
-                          const cs_traj_out& o, hipStream_t s)
-{
-#define C_(G) rollout_g<G>(b, T, seed, t0, env_base, o, s)
-    if (b.game == CS_GAME_DOUDIZHU) return ddz::launch_rollout(b, T, seed, t0, env_base, o, s);
-    if (is_blackjack_shoe(b)) return bjs_launch_rollout(b, T, seed, t0, env_base, o, s);
-    if (is_holdem_n(b)) return np_launch_rollout(b, T, seed, t0, env_base, o, s);
-    CS_DISPATCH(b.game, C_)
-#undef C_
 }
 
 }  // namespace cs

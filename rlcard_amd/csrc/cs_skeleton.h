@@ -1,7 +1,8 @@
 // cs_skeleton.h -- the lockstep kernel skeleton shared by every lane-per-env game (one lane = one env, one wave = EPW
 // consecutive envs): k_seed / k_reset / k_step / k_observe / k_rollout over a Game type (cs_leduc.h, cs_limit.h,
-// cs_nolimit.h, cs_blackjack.h, cs_holdem_n.h) and their host launchers. Included by the translation units that
-// instantiate games (cs_kernels.hip: the heads-up / single-table games; cs_holdem_n.hip: 3..6-player hold'em).
+// cs_nolimit.h, cs_blackjack.h, cs_holdem_n.h), their host launchers and ops_of<G>, the game's launch table entry
+// (cs_engine.h GameOps). Included by the translation units that instantiate games (cs_kernels.hip: the heads-up /
+// single-table games; cs_holdem_n*.hip: 3..22-player hold'em).
 // Integer/branchy work: no MFMA. The bound is HBM (obs/legal/reward rows out, packed state + RNG words in/out).
 #pragma once
 #include <cstddef>
@@ -707,6 +708,19 @@ static void fill_info(cs_game_info* info)
 }
 
 template <class G>
-static int64_t stage_bytes_of() { return G::STAGE_MODE == STAGE_LDS ? G::STAGE_W : 0; }
+static int32_t stage_bytes_of() { return G::STAGE_MODE == STAGE_LDS ? G::STAGE_W : 0; }
+
+// The launch table entry (cs_engine.h) of skeleton game G. Naming it instantiates the five kernels for G.
+template <class G>
+static const GameOps* ops_of()
+{
+    static const GameOps ops = [] {
+        GameOps o{seed_g<G>, reset_g<G>, step_g<G>, observe_g<G>, rollout_g<G>, {}, stage_bytes_of<G>(),
+                  RING_ENV_WORDS, false, false};
+        fill_info<G>(&o.info);
+        return o;
+    }();
+    return &ops;
+}
 
 }  // namespace cs

@@ -279,10 +279,10 @@ __global__ void k_copy_state(const uint32_t* __restrict__ st, int64_t n, int64_t
     if (w < sw) dst[w] = env_major ? st[env * sw + w] : st[(int64_t)w * n + env];
 }
 
-hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, uint32_t* dst, hipStream_t s)
+hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, int32_t env_major, uint32_t* dst,
+                             hipStream_t s)
 {
-    hipLaunchKernelGGL(k_copy_state, dim3(1), dim3(64), 0, s, b.state, b.n, env, sw, state_env_major(b.game) ? 1 : 0,
-                       dst);
+    hipLaunchKernelGGL(k_copy_state, dim3(1), dim3(64), 0, s, b.state, b.n, env, sw, env_major, dst);
     return hipGetLastError();
 }
 

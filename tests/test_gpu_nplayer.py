@@ -116,6 +116,46 @@ def test_nplayer_rollout_matches_oracle(oracle, game, players, cfg, flags):
         assert v.rng_position(i) == ob.draws(i) % v.rng_period
 
 
+# the first player count each translation unit serves (cs_holdem_n10 / n16 / n22.hip), and Blackjack on either side of
+# the byte-ring / shoe boundary (cs_blackjack.h up to 4 players and one deck, cs_blackjack_shoe.hip beyond)
+EDGES = [('limit-holdem', 7, 1), ('no-limit-holdem', 7, 1), ('limit-holdem', 11, 1), ('no-limit-holdem', 11, 1),
+         ('limit-holdem', 17, 1), ('no-limit-holdem', 17, 1), ('blackjack', 4, 1), ('blackjack', 5, 1),
+         ('blackjack', 1, 2)]
+
+
+@pytest.mark.parametrize('game,players,decks', EDGES)
+def test_launch_table_edges_match_oracle(oracle, game, players, decks):
+    """The lowest config of each range of the engine's launch table (cs_engine.h find_game), where a lookup could pick
+    the wrong unit: reset, steps (illegal ids included), every player's observation, then one rollout, on two full
+    waves and a partial one."""
+    n, T = 130, 16
+    cfg = {'game_num_players': players}
+    if game == 'blackjack':
+        cfg['game_num_decks'] = decks
+    v = _vec(game, n, seed=40, config=cfg)
+    assert v.num_players == players
+    keys, lens = seeding.seed_keys(range(40, 40 + n))
+    ob = oracle.Batch(game, n, keys, lens, num_players=players, num_decks=decks)
+    rng = np.random.RandomState(2)
+    _same(_np(v.reset()), ob.reset(), 'reset')
+    for t in range(12):
+        acts = rng.randint(-1, v.num_actions + 1, size=n).astype(np.int32)   # includes illegal ids
+        _same(_np(v.step(torch.from_numpy(acts).cuda())), ob.step(acts), 'step %d' % t)
+    for p in range(players):
+        o = _np(v.observe(p))
+        for i in range(n):
+            obs, legal = ob.observe(i, p)
+            assert np.array_equal(o['obs'][i], obs) and np.array_equal(o['legal'][i], legal), (p, i)
+    got = _np(v.rollout(T, policy_seed=5, final_obs=True))
+    exp = ob.rollout(T, 5, 0, 0, final_obs=True)
+    done = exp['done'].astype(bool)
+    got['final_obs'], exp['final_obs'] = got['final_obs'][done], exp['final_obs'][done]
+    _same(got, exp, 'rollout')
+    torch.cuda.synchronize()
+    for i in (0, 63, 64, 128, n - 1):
+        assert v.rng_position(i) == ob.draws(i) % v.rng_period
+
+
 @pytest.mark.parametrize('game,players', [('leduc-holdem', 4), ('limit-holdem', 5), ('no-limit-holdem', 6),
                                           ('limit-holdem', 22), ('no-limit-holdem', 17)])
 def test_nplayer_compat_env(game, players):
