@@ -69,7 +69,9 @@ typedef struct {
 } cs_game_info;
 /* cs_game_info grows at its end between ABI versions (2: game_words, deal_queue_depth, envs_per_wave; 3 adds the
  * cs_state_* functions); a consumer built against this header checks cs_abi_version() >= CS_ABI_VERSION before
- * calling cs_game_info_get, which writes sizeof(cs_game_info) bytes of this version. */
+ * calling cs_game_info_get, which writes sizeof(cs_game_info) bytes of this version. Functions added without a
+ * layout change keep the version (cs_rollout_policy, cs_policy_actions, cs_payoff_sums): a consumer that may meet an
+ * older library looks the symbol up. */
 #define CS_ABI_VERSION 3
 
 /* Outputs of reset/step/observe, all device pointers, one row per env:
@@ -156,6 +158,44 @@ int cs_observe(cs_handle* h, int32_t player, const cs_step_out* out, void* strea
  * Replaces T iterations of the Env.run loop (envs/env.py:120-169) for every env. */
 int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint64_t env_base, const cs_traj_out* out,
                void* stream);
+
+/* Policies the engine can play on the device, per seat of cs_rollout_policy or for the acting player of
+ * cs_policy_actions. The rule policies restate the reference's rule models (rlcard/models/leducholdem_rule_models.py,
+ * limitholdem_rule_models.py; the Python forms are rlcard_amd.models) on the packed game state:
+ *   CS_POLICY_RANDOM   uniform over the legal actions, the policy of cs_rollout (same Philox counter, same pick)
+ *   CS_POLICY_RULE_V1  Leduc: leduc-holdem-rule-v1 (raise, else call, else check, else fold);
+ *                      Limit: limit-holdem-rule-v1 (hole-card classes against the board's ranks and suits)
+ *   CS_POLICY_RULE_V2  Leduc only: leduc-holdem-rule-v2 (raise on a rank match with the public card, else fold)
+ * A rule that aims at an illegal action plays call for raise, fold for check and raise for call, as the reference does.
+ * Rule policies exist for default 2-player Leduc and heads-up Limit hold'em; with any other game or player count a
+ * rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit). */
+enum { CS_POLICY_RANDOM = 0, CS_POLICY_RULE_V1 = 1, CS_POLICY_RULE_V2 = 2 };
+
+/* cs_rollout with seat p playing seat_policy[p] (HOST array of num_players CS_POLICY_* ids): the way to play a fixed
+ * baseline -- Env.run with models.load(name).agents (rlcard/utils/utils.py tournament) -- in the fused rollout. A
+ * random seat picks exactly what cs_rollout picks at the same (policy_seed, env_base + env, t0 + t) and legal set, so
+ * an all-random seat_policy gives cs_rollout's trajectory and end state byte for byte; a rule seat reads the env's game
+ * state and draws nothing. Same outputs as cs_rollout. */
+int cs_rollout_policy(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint64_t env_base,
+                      const int32_t* seat_policy, const cs_traj_out* out, void* stream);
+
+/* The action `policy` takes for the current player of every env, without changing any state: actions int32 [n]
+ * (DEVICE), -1 where the env's game is over (cs_step ignores that env's action and starts its next game). A random
+ * pick is the one cs_rollout_policy makes at step counter t. Lets a learner stepping with cs_step take its opponents'
+ * moves on the device (agent.eval_step of a rule agent for every env at once). */
+int cs_policy_actions(cs_handle* h, int32_t policy, uint64_t policy_seed, uint64_t t, uint64_t env_base,
+                      int32_t* actions, void* stream);
+
+/* Tournament sums of a rollout trajectory of this handle (rlcard/utils/utils.py:200-225 tournament, for every env at
+ * once): the payoff rows of the games that end inside `traj` (needs reward and done, [T][n] rows) are added to sums
+ * (double [num_players], DEVICE) and counted in *games (int64, DEVICE), env e contributing a game only while
+ * games_per_env[e] (int32 [n], DEVICE) is below `quota`, and counting it there. All three accumulate across calls (zero
+ * them first), so over consecutive windows every env contributes exactly its first `quota` games: which games count
+ * does not depend on where the windows end, and short games are not favoured. quota <= 0: no limit. The sums are exact
+ * and independent of the order of addition wherever the payoffs are multiples of a power of two (every game here: see
+ * cs_step_out reward). */
+int cs_payoff_sums(cs_handle* h, int32_t T, const cs_traj_out* traj, int32_t quota, int32_t* games_per_env,
+                   double* sums, int64_t* games, void* stream);
 
 /* Placement probe of a trajectory allocation: zeros written into every non-NULL tensor of `out` ([T][n] rows, the
  * cs_rollout layout) in the rollout's write order, without game logic or state change. Where a trajectory lands in HBM

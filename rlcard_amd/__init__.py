@@ -9,3 +9,4 @@ __version__ = '0.1.0'
 
 from .vec import VecEnv, legal_mask, legal_ids  # noqa: F401
 from .envs import make, register  # noqa: F401
+from . import models  # noqa: F401

@@ -60,9 +60,12 @@ SYMBOLS = ('cs_game_info_get', 'cs_create', 'cs_destroy', 'cs_seed', 'cs_reset',
            'cs_debug_set_serial_refill', 'cs_debug_set_kernel_flags',
            'cs_dmc_create', 'cs_dmc_destroy', 'cs_dmc_fill', 'cs_dmc_gather', 'cs_dmc_status', 'cs_dmc_layer1',
            'cs_dmc_select', 'cs_last_error', 'cs_version', 'cs_abi_version', 'cs_state_bytes', 'cs_state_save',
-           'cs_state_load')
+           'cs_state_load', 'cs_rollout_policy', 'cs_policy_actions', 'cs_payoff_sums')
 # symbols an older library build may lack (A/B builds loaded with CARDSIM_LIB); callers check hasattr(lib(), name)
-OPTIONAL = ('cs_traj_probe', 'cs_state_bytes', 'cs_state_save', 'cs_state_load')
+OPTIONAL = ('cs_traj_probe', 'cs_state_bytes', 'cs_state_save', 'cs_state_load', 'cs_rollout_policy',
+            'cs_policy_actions', 'cs_payoff_sums')
+
+POLICY_RANDOM, POLICY_RULE_V1, POLICY_RULE_V2 = 0, 1, 2   # CS_POLICY_* (rlcard_amd.models gives them names)
 
 _lib = None
 
@@ -95,6 +98,10 @@ def lib():
         L.cs_state_bytes.argtypes = [vp, vp]
         L.cs_state_save.argtypes = [vp, vp, vp]
         L.cs_state_load.argtypes = [vp, vp, vp]
+    if hasattr(L, 'cs_rollout_policy'):   # (added without an ABI version change: found by symbol)
+        L.cs_rollout_policy.argtypes = [vp, i32, u64, u64, u64, vp, C.POINTER(TrajOut), vp]
+        L.cs_policy_actions.argtypes = [vp, i32, u64, u64, u64, vp, vp]
+        L.cs_payoff_sums.argtypes = [vp, i32, C.POINTER(TrajOut), i32, vp, vp, vp, vp]
     L.cs_transitions.argtypes = [vp, i32, C.POINTER(TrajOut), C.POINTER(TransOut), vp]
     L.cs_legal_lists.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.cs_action_features.argtypes = [vp, vp, i64, vp, vp]

@@ -257,6 +257,64 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_rollout");
 }
 
+int cs_rollout_policy(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint64_t env_base,
+                      const int32_t* seat_policy, const cs_traj_out* out, void* stream)
+{
+    if (!h || !out || !seat_policy) return fail(CS_E_INVALID, "null argument");
+    if (!out->obs || !out->legal || !out->player || !out->action || !out->reward || !out->done)
+        return fail(CS_E_INVALID, "cs_rollout_policy needs every trajectory buffer");
+    if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
+    const int32_t P = h->ops->info.num_players;
+    bool rules = false;
+    for (int32_t p = 0; p < P; p++) {
+        if (seat_policy[p] < CS_POLICY_RANDOM || seat_policy[p] > CS_POLICY_RULE_V2)
+            return fail(CS_E_INVALID, "unknown policy id");
+        rules |= seat_policy[p] != CS_POLICY_RANDOM;
+    }
+    if (!h->seeded) return fail(CS_E_STATE, "cs_rollout_policy before cs_seed");
+    int r = set_device(h);
+    if (r != CS_OK) return r;
+    hipError_t e;
+    if (!rules && !h->ops->rollout_policy) {   // every seat random on a game without policy kernels: cs_rollout
+        e = h->ops->rollout(h->b, T, policy_seed, t0, env_base, *out, (hipStream_t)stream);
+    } else {
+        uint32_t seats = 0;
+        for (int32_t p = 0; p < P; p++) {
+            if (!h->ops->rollout_policy || seat_policy[p] > h->ops->max_policy)
+                return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2) and limit-holdem (v1) only");
+            seats |= (uint32_t)seat_policy[p] << (8 * p);   // (P = 2 wherever rollout_policy is set)
+        }
+        e = h->ops->rollout_policy(h->b, T, policy_seed, t0, env_base, seats, *out, (hipStream_t)stream);
+    }
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_rollout_policy");
+}
+
+int cs_policy_actions(cs_handle* h, int32_t policy, uint64_t policy_seed, uint64_t t, uint64_t env_base,
+                      int32_t* actions, void* stream)
+{
+    if (!h || !actions) return fail(CS_E_INVALID, "null argument");
+    if (policy < CS_POLICY_RANDOM || policy > CS_POLICY_RULE_V2) return fail(CS_E_INVALID, "unknown policy id");
+    if (!h->ops->policy_actions || policy > h->ops->max_policy)
+        return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2) and limit-holdem (v1) only");
+    if (!h->seeded) return fail(CS_E_STATE, "cs_policy_actions before cs_seed");
+    int r = set_device(h);
+    if (r != CS_OK) return r;
+    hipError_t e = h->ops->policy_actions(h->b, policy, policy_seed, t, env_base, actions, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_policy_actions");
+}
+
+int cs_payoff_sums(cs_handle* h, int32_t T, const cs_traj_out* traj, int32_t quota, int32_t* games_per_env,
+                   double* sums, int64_t* games, void* stream)
+{
+    if (!h || !traj || !games_per_env || !sums || !games) return fail(CS_E_INVALID, "null argument");
+    if (!traj->reward || !traj->done) return fail(CS_E_INVALID, "traj needs reward and done");
+    if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
+    int r = set_device(h);
+    if (r != CS_OK) return r;
+    hipError_t e = cs::launch_payoff_sums(h->b, T, *traj, quota, games_per_env, sums, games, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_payoff_sums");
+}
+
 // ---- DMC ----------------------------------------------------------------------------------------------------------
 struct cs_dmc {
     cs_handle* h;

@@ -71,6 +71,13 @@ struct GameOps {
     int32_t mt_words;       // u32 per env in Buffers::mt
     bool mt_columns;        // word k of env e at mt[k * n + e] (the shoe) instead of mt[e * mt_words + k]
     bool env_major;         // state is [n][state_words] (DouDizhu) instead of [state_words][n]
+    // Rule policies (include/cardsim.h CS_POLICY_*), null where the type has none (every positional initialiser above
+    // leaves them so): the rollout with seat p playing byte p of `seats`, and one policy's action per env
+    hipError_t (*rollout_policy)(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
+                                 uint32_t seats, const cs_traj_out& o, hipStream_t s);
+    hipError_t (*policy_actions)(const Buffers& b, int32_t policy, uint64_t seed, uint64_t t, uint64_t env_base,
+                                 int32_t* actions, hipStream_t s);
+    int32_t max_policy;     // largest CS_POLICY_* id the two launchers take
 };
 
 // The type that serves `cfg` (null: the game's defaults), or null where the engine has none (cs_kernels.hip). The
@@ -115,6 +122,8 @@ hipError_t launch_traj_probe(const Buffers& b, int32_t T, const cs_traj_out& tr,
                              int32_t action_bytes, int32_t epw, hipStream_t s);
 hipError_t launch_transitions(const Buffers& b, int32_t T, const cs_traj_out& tr, const cs_trans_out& o,
                               hipStream_t s);
+hipError_t launch_payoff_sums(const Buffers& b, int32_t T, const cs_traj_out& tr, int32_t quota, int32_t* games_per_env,
+                              double* sums, int64_t* games, hipStream_t s);
 hipError_t launch_legal_lists(const Buffers& b, int32_t lb, const uint8_t* legal, int64_t rows, int32_t* counts,
                               int64_t* offsets, int32_t* ids, void** tmp, size_t* tmp_bytes, hipStream_t s);
 hipError_t launch_onehot(const int32_t* ids, int64_t count, int32_t na, uint8_t* out, hipStream_t s);

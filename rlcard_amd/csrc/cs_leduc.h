@@ -14,6 +14,7 @@
 //   w1: round_counter:2 pointer:1 folded0:1 folded1:1
 #pragma once
 #include "cs_device.h"
+#include "../../include/cardsim.h"
 
 #include "cs_prof.h"
 
@@ -65,6 +66,21 @@ struct Leduc {
         if (rp < mx) m &= ~(1u << CHECK);
         if (rp == mx) m &= ~(1u << CALL);
         return m;
+    }
+
+    // The rule models of rlcard/models/leducholdem_rule_models.py for seat `player` with legal set `lg`, on the cards
+    // in registers (card = 2 * rank + suit): v1 plays the most aggressive legal action; v2 raises when the public card
+    // is out and pairs the hand (call where the round's raises are spent: its raise -> call fallback) and folds
+    // otherwise -- before the public card too, where the reference tests the hand's suit letter against 'K' / 'Q'.
+    // Selects, no branches: both answers are a few lane operations.
+    static constexpr int MAX_POLICY = CS_POLICY_RULE_V2;
+    __device__ __forceinline__ int rule_action(uint32_t policy, int player, uint32_t lg) const
+    {
+        const int hand = player ? h1 : h0;
+        const int v1 = (lg >> RAISE) & 1u ? RAISE : ((lg >> CALL) & 1u ? CALL : ((lg >> CHECK) & 1u ? CHECK : FOLD));
+        const bool pairs = rc >= 1 && ((pub ^ hand) >> 1) == 0;
+        const int v2 = pairs ? ((lg >> RAISE) & 1u ? RAISE : CALL) : FOLD;
+        return policy == CS_POLICY_RULE_V2 ? v2 : v1;
     }
 
     __device__ __forceinline__ void observe(int player, uint32_t (&bits)[NB]) const

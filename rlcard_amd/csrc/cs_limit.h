@@ -24,6 +24,7 @@
 //   w3: raise_nums 4x3 (0..11), prev_raise_nums 4x3 (12..23)
 #pragma once
 #include "cs_device.h"
+#include "../../include/cardsim.h"
 
 namespace cs {
 
@@ -320,6 +321,45 @@ struct Limit {
         if (rp < mx) m &= ~(1u << CHECK);
         if (rp == mx) m &= ~(1u << CALL);
         return m;
+    }
+
+    // The rule model of rlcard/models/limitholdem_rule_models.py (limit-holdem-rule-v1) for seat `player` with legal
+    // set `lg`, on rank and suit masks of the 6-bit cards (id = suit * 13 + rank, rank 0 = A, 1..8 = 2..9, 9..12 =
+    // T J Q K): the hole cards' rank mask, and the rank and suit masks of the board cards the round has shown.
+    //   a pair raises before the flop, later when the board holds its rank;
+    //   an ace with a T..K kicker raises before the flop, later when the board holds any of A T J Q K; with a smaller
+    //   kicker it needs the hole cards suited, and later that suit on the board;
+    //   any other hand raises before the flop when both hole cards are T..K; later it calls, unless every board card
+    //   is a 2..5 (the reference's string maximum of the board's rank characters lying in '2'..'5'): then it checks
+    //   on the flop and folds after it.
+    // Everything else folds; an illegal aim falls back raise -> call, check -> fold, call -> raise. Every class is
+    // computed and selected (no divergence on the hand class).
+    static constexpr int MAX_POLICY = CS_POLICY_RULE_V1;
+    __device__ __forceinline__ int rule_action(uint32_t, int player, uint32_t lg) const
+    {
+        constexpr uint32_t TK = 0x1E00u, HIGH = TK | 1u, LOW = 0x1Eu;   // ranks T..K; A and T..K; 2..5
+        const uint32_t c0 = (uint32_t)hole(player, 0), c1 = (uint32_t)hole(player, 1);
+        const uint32_t s0 = (c0 * 5u) >> 6, s1 = (c1 * 5u) >> 6;       // id / 13 for id < 64
+        const uint32_t q0 = c0 - 13u * s0, q1 = c1 - 13u * s1;
+        const uint32_t hm = 1u << q0 | 1u << q1;
+        const int r = rc(), npub = r == 0 ? 0 : (r == 1 ? 3 : (r == 2 ? 4 : 5));
+        uint32_t brm = 0, bsm = 0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const uint32_t c = (uint32_t)board(k), s = (c * 5u) >> 6, on = (uint32_t)(k < npub);
+            brm |= on << (c - 13u * s);
+            bsm |= on << s;
+        }
+        const bool pair = q0 == q1, ace = (hm & 1u) != 0u, kicker = (hm & TK) != 0u, suited = s0 == s1;
+        const bool both_tk = ((TK >> q0) & (TK >> q1) & 1u) != 0u;
+        const bool pre = pair || (ace ? (kicker || suited) : both_tk);
+        const bool hit = pair ? ((brm >> q0) & 1u) != 0u
+                              : (kicker ? (brm & HIGH) != 0u : (suited && ((bsm >> s0) & 1u) != 0u));
+        const int other = (brm & ~LOW) == 0u ? (npub == 3 ? CHECK : FOLD) : CALL;
+        const int post = (pair || ace) ? (hit ? RAISE : FOLD) : other;
+        const int aim = npub == 0 ? (pre ? RAISE : FOLD) : post;
+        const int fb = (0x2201 >> (4 * aim)) & 3;                      // call -> raise, raise -> call, fold, check -> fold
+        return (lg >> aim) & 1u ? aim : fb;
     }
 
     // the cards as a 64-bit mask (ids < 52), the four raise one-hots as a 20-bit field at obs bit 52

@@ -462,17 +462,33 @@ struct RolloutArgs {
     uint32_t* sctl;
     uint8_t* sbuf;
     int32_t T, flags;
+    uint32_t seats;   // k_rollout<G, true>: byte p = seat p's CS_POLICY_* id (one scalar word for the per-step choice)
+    uint32_t pad_;
 };
 typedef const __attribute__((address_space(4))) RolloutArgs* RolloutArgsK;
-// k_rollout reads its argument back through __builtin_amdgcn_kernarg_segment_ptr(), so RolloutArgs must stay the
-// kernel's ONLY explicit parameter (then it sits at kernarg offset 0 with exactly the host layout): any new argument
-// goes inside the struct
+// k_rollout (either instantiation) reads its argument back through __builtin_amdgcn_kernarg_segment_ptr(), so
+// RolloutArgs must stay the kernel's ONLY explicit parameter (then it sits at kernarg offset 0 with exactly the host
+// layout): any new argument goes inside the struct
 static_assert(std::is_standard_layout<RolloutArgs>::value && std::is_trivially_copyable<RolloutArgs>::value,
               "RolloutArgs is copied into the kernarg segment bytewise");
 static_assert(offsetof(RolloutArgs, mt) == 0 && alignof(RolloutArgs) == 8 && sizeof(RolloutArgs) % 8 == 0,
               "RolloutArgs: first kernarg at offset 0, 8-byte aligned");
 
+// games with rule policies (G::MAX_POLICY, G::rule_action: cs_leduc.h, cs_limit.h)
+template <class G, class = void>
+struct MaxPolicy {
+    static constexpr int value = 0;
+};
 template <class G>
+struct MaxPolicy<G, std::void_t<decltype(G::MAX_POLICY)>> {
+    static constexpr int value = G::MAX_POLICY;
+};
+
+// The rollout. POL = false (cs_rollout) plays the uniform-random policy; POL = true (cs_rollout_policy) is a second
+// instantiation in which seat p plays byte p of args.seats (CS_POLICY_*). Everything the policy path adds sits inside
+// `if constexpr (POL)`, so the random rollout -- tuned to its register budget, see the comments below -- compiles from
+// the same statements as before the policy path existed.
+template <class G, bool POL = false>
 __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs args)
 {
     RolloutArgsK ak = (RolloutArgsK)__builtin_amdgcn_kernarg_segment_ptr();
@@ -566,6 +582,14 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
         int a;
         if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
         else a = G::A <= 32 ? pick_legal32((uint32_t)lg, pr) : pick_legal(lg, pr);
+        if constexpr (POL) {
+            // the seats' policies are one word of the argument block (a scalar load); the acting seat's byte picks
+            // between the random pick above -- always made, at cs_rollout's counter, so random seats play the same
+            // games -- and the rule's answer on the state in registers. A rule seat draws nothing.
+            const uint32_t pid = (A.seats >> (8 * p)) & 0xFFu;
+            const int ra = g.rule_action(pid, p, (uint32_t)lg);
+            a = pid == (uint32_t)CS_POLICY_RANDOM ? a : ra;
+        }
 #if !CS_PROF_NO_OBS
         if constexpr (SparseObs<G>::value) {
             uint32_t pos[SparseK<G>::value];
@@ -643,6 +667,28 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
     }
 }
 
+// cs_policy_actions: what `policy` plays for the current player of each env, -1 where the game is over; no state or
+// stream is written. The random pick is the rollout's at step counter t (philox_u32 = PolicyRng::at).
+template <class G>
+__global__ __launch_bounds__(BLOCK) void k_policy_actions(const uint32_t* st, int64_t n, int policy, uint64_t seed,
+                                                           uint64_t t, uint64_t env_base, int32_t* actions,
+                                                           GameParams prm)
+{
+    const int64_t env = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (env >= n) return;
+    G g;
+    g.bind(nullptr, prm);
+    g.blank();
+    g.load(st, n, env);
+    int a = -1;
+    if (!g.is_over()) {
+        const uint32_t lg = (uint32_t)g.legal();
+        if (policy == CS_POLICY_RANDOM) a = pick_legal_small<G::A>(lg, philox_u32(seed, env_base + (uint64_t)env, t));
+        else a = g.rule_action((uint32_t)policy, g.current(), lg);
+    }
+    actions[env] = a;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 static inline GameParams params_of(const Buffers& b)
 {
@@ -692,6 +738,24 @@ static hipError_t rollout_g(const Buffers& b, int32_t T, uint64_t seed, uint64_t
 }
 
 template <class G>
+static hipError_t rollout_policy_g(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
+                                   uint32_t seats, const cs_traj_out& o, hipStream_t s)
+{
+    const RolloutArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, params_of(b), b.sctl, b.sbuf, T, b.serial_refill,
+                        seats, 0u};
+    hipLaunchKernelGGL((k_rollout<G, true>), grid_for(b.n, G::EPW), dim3(BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+template <class G>
+static hipError_t policy_actions_g(const Buffers& b, int32_t policy, uint64_t seed, uint64_t t, uint64_t env_base,
+                                   int32_t* actions, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_policy_actions<G>, dim3((unsigned)((b.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, b.state,
+                       b.n, policy, seed, t, env_base, actions, params_of(b));
+    return hipGetLastError();
+}
+
+template <class G>
 static void fill_info(cs_game_info* info)
 {
     info->obs_dim = G::OBS;
@@ -710,7 +774,8 @@ static void fill_info(cs_game_info* info)
 template <class G>
 static int32_t stage_bytes_of() { return G::STAGE_MODE == STAGE_LDS ? G::STAGE_W : 0; }
 
-// The launch table entry (cs_engine.h) of skeleton game G. Naming it instantiates the five kernels for G.
+// The launch table entry (cs_engine.h) of skeleton game G. Naming it instantiates the five kernels for G (and the two
+// policy kernels of a game with rule policies).
 template <class G>
 static const GameOps* ops_of()
 {
@@ -718,6 +783,11 @@ static const GameOps* ops_of()
         GameOps o{seed_g<G>, reset_g<G>, step_g<G>, observe_g<G>, rollout_g<G>, {}, stage_bytes_of<G>(),
                   RING_ENV_WORDS, false, false};
         fill_info<G>(&o.info);
+        if constexpr (MaxPolicy<G>::value > 0) {   // naming them instantiates the two policy kernels for G
+            o.rollout_policy = rollout_policy_g<G>;
+            o.policy_actions = policy_actions_g<G>;
+            o.max_policy = MaxPolicy<G>::value;
+        }
         return o;
     }();
     return &ops;

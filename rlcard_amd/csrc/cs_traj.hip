@@ -66,6 +66,60 @@ __global__ __launch_bounds__(TBLOCK) void k_transitions(const uint8_t* __restric
     }
 }
 
+// ---- tournament sums (cs_payoff_sums) ------------------------------------------------------------------------------
+// One lane per env scans its T done bytes in time order and adds the payoff row of every finished game that still fits
+// the env's quota (games_per_env[e] < quota before it; quota <= 0: every game), four seats per pass in registers. A
+// wave then reduces its lanes' partial sums by shuffles and issues one atomic per seat, plus one for the game count.
+// The order of these additions is not fixed, and need not be: every payoff here is a multiple of 0.25 (Leduc 0.5 heads-
+// up, Limit 0.5 big blinds, whole chips or +-1 / 0 elsewhere: include/cardsim.h cs_step_out reward), so every partial
+// sum is a multiple of 0.25 far below 2^52 of them and fp64 holds it exactly: the result does not depend on the order.
+__global__ __launch_bounds__(TBLOCK) void k_payoff_sums(const uint8_t* __restrict__ done,
+                                                        const float* __restrict__ reward, int T, int64_t n, int P,
+                                                        int quota, int32_t* games_per_env, double* sums,
+                                                        unsigned long long* games)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t e = (int64_t)blockIdx.x * TBLOCK + threadIdx.x;
+    const bool valid = e < n;   // (no early return: every lane takes part in the shuffles)
+    const int cnt0 = valid ? games_per_env[e] : 0;
+    for (int q0 = 0; q0 < P; q0 += 4) {
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        int cnt = cnt0;
+        if (valid) {
+            for (int t = 0; t < T; t++) {
+                const int64_t row = (int64_t)t * n + e;
+                if (done[row] && (quota <= 0 || cnt < quota)) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        if (q0 + k < P) acc[k] += (double)reward[row * P + q0 + k];
+                    cnt++;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            double v = acc[k];
+            for (int o = WAVE / 2; o; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0 && q0 + k < P && v != 0.0) atomicAdd(sums + q0 + k, v);
+        }
+        if (q0 == 0) {   // the same games count in every pass: counted and recorded once
+            int ng = cnt - cnt0;
+            for (int o = WAVE / 2; o; o >>= 1) ng += __shfl_xor(ng, o);
+            if (lane == 0 && ng) atomicAdd(games, (unsigned long long)ng);
+            if (valid) games_per_env[e] = cnt;
+        }
+    }
+}
+
+hipError_t launch_payoff_sums(const Buffers& b, int32_t T, const cs_traj_out& tr, int32_t quota, int32_t* games_per_env,
+                              double* sums, int64_t* games, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_payoff_sums, dim3((unsigned)((b.n + TBLOCK - 1) / TBLOCK)), dim3(TBLOCK), 0, s,
+                       (const uint8_t*)tr.done, (const float*)tr.reward, T, b.n, b.num_players, quota, games_per_env,
+                       sums, (unsigned long long*)games);
+    return hipGetLastError();
+}
+
 // ---- legal lists ------------------------------------------------------------------------------------------------
 // short rows (<= 16 bytes: leduc / limit / blackjack): one lane per row
 __global__ __launch_bounds__(TBLOCK) void k_legal_count_small(const uint8_t* __restrict__ legal, int64_t rows, int lb,

@@ -60,6 +60,28 @@ def tournament(env, num):
     return list(total / games)
 
 
+def tournament_vec(vec_env, policies, games_per_env, T=64, policy_seed=0):
+    """tournament for a VecEnv, on the device: seat p plays policies[p] (names, engine ids or agents with policy_id, as
+    VecEnv.rollout takes them) in windows of T fused steps until every env has finished games_per_env games; the mean
+    payoff per seat over exactly the first games_per_env games of every env, as a list. The payoffs are summed on the
+    device (VecEnv.payoff_sums); the host reads back one scalar per window, the smallest per-env game count. Counting
+    each env's first games, not the games finished when the last window ends, keeps short games from being favoured
+    and makes the result independent of T."""
+    quota = int(games_per_env)
+    if quota <= 0:
+        raise ValueError('games_per_env must be positive')
+    traj = vec_env.new_traj_out(T, select=1)
+    acc = vec_env.new_payoff_sums()
+    t0 = 0
+    while True:
+        vec_env.rollout(T, policy_seed=policy_seed, t0=t0, out=traj, policies=policies)
+        vec_env.payoff_sums(traj, acc, quota)
+        t0 += T
+        if int(acc['games_per_env'].min().item()) >= quota:
+            break
+    return list((acc['sums'] / acc['games'].to(acc['sums'].dtype)).cpu().numpy())
+
+
 # ---- PettingZoo-side helpers (rlcard/utils/pettingzoo_utils.py:5-72) --------------------------------------------------
 # They drive any env with PettingZoo's AEC protocol: reset(), agent_iter(), last() -> (observation, reward, termination,
 # truncation, info), step(action); observations are {'observation': ..., 'action_mask': ...}. pettingzoo itself is not

@@ -264,17 +264,72 @@ class VecEnv:
             e1.synchronize()
         return e0.elapsed_time(e1)
 
-    def rollout(self, T, policy_seed=0, t0=0, out=None, final_obs=False):
+    def rollout(self, T, policy_seed=0, t0=0, out=None, final_obs=False, policies=None):
         """T lockstep steps of the uniform-random legal policy, auto-reset; -> trajectory dict of [T, N, ...]
         (+ 'final_obs' [T, N, P, obs_dim] where a game ended, when asked for or present in `out`). Without `out`,
-        the trajectory comes from new_traj_out (placement chosen); pass `out` to reuse one across launches."""
+        the trajectory comes from new_traj_out (placement chosen); pass `out` to reuse one across launches.
+        policies: one entry per seat -- a name ('random', 'leduc-holdem-rule-v1', ...), an engine policy id or an agent
+        with policy_id (rlcard_amd.models) -- played on the device (cs_rollout_policy); random seats pick what the plain
+        rollout picks. None: the plain rollout (cs_rollout)."""
         o = out if out is not None else self.new_traj_out(T, final_obs)
         s = _abi.TrajOut(_ptr(o['obs']), _ptr(o['legal']), _ptr(o['player']), _ptr(o['action']),
                          _ptr(o['reward']), _ptr(o['done']), _ptr(o.get('final_obs')))
+        seed = int(policy_seed) & (2 ** 64 - 1)
         with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_rollout(self._h, int(T), int(policy_seed) & (2 ** 64 - 1), int(t0),
-                                             self.env_base, C.byref(s), self._stream()), 'cs_rollout')
+            if policies is None:
+                _abi.check(_abi.lib().cs_rollout(self._h, int(T), seed, int(t0), self.env_base, C.byref(s),
+                                                 self._stream()), 'cs_rollout')
+            else:
+                seats = self._seat_policies(policies)
+                _abi.check(self._policy_fn('cs_rollout_policy')(self._h, int(T), seed, int(t0), self.env_base, seats,
+                                                                C.byref(s), self._stream()), 'cs_rollout_policy')
         return o
+
+    # -- policies on the device (include/cardsim.h CS_POLICY_*) --------------------------------------------------------
+    @staticmethod
+    def _policy_fn(name):
+        L = _abi.lib()
+        if not hasattr(L, name):   # an older A/B build: an error, never a host fallback
+            raise _abi.CardsimError('%s lacks %s' % (_abi.LIB_PATH, name))
+        return getattr(L, name)
+
+    def _seat_policies(self, policies):
+        from .models import policy_id_of
+        ids = [policy_id_of(p) for p in policies]
+        if len(ids) != self.num_players:
+            raise ValueError('expected %d policies (one per seat), got %d' % (self.num_players, len(ids)))
+        return (C.c_int32 * len(ids))(*ids)
+
+    def policy_actions(self, policy, policy_seed=0, t=0, out=None):
+        """The action `policy` (name, id or agent, as rollout's) takes for the current player of every env, computed on
+        the device without changing state: int32 [N], -1 where the env's game is over (step() ignores that action and
+        starts the next game). 'random' picks what rollout(policies=...) picks at step counter t."""
+        from .models import policy_id_of
+        a = out if out is not None else torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self._policy_fn('cs_policy_actions')(self._h, policy_id_of(policy),
+                                                            int(policy_seed) & (2 ** 64 - 1), int(t), self.env_base,
+                                                            _ptr(a), self._stream()), 'cs_policy_actions')
+        return a
+
+    def new_payoff_sums(self):
+        """Zeroed accumulators of payoff_sums: per-env game counts, per-seat payoff sums, the number of games."""
+        d = self.device
+        return dict(games_per_env=torch.zeros(self.num_envs, dtype=torch.int32, device=d),
+                    sums=torch.zeros(self.num_players, dtype=torch.float64, device=d),
+                    games=torch.zeros(1, dtype=torch.int64, device=d))
+
+    def payoff_sums(self, traj, acc, quota=0):
+        """Adds the payoffs of the games that end inside trajectory `traj` into `acc` (new_payoff_sums) on the device
+        (cs_payoff_sums): env e contributes a game only while acc['games_per_env'][e] < quota (quota <= 0: always), so
+        over consecutive windows every env contributes exactly its first `quota` games."""
+        T = traj['done'].shape[0]
+        tr = _abi.TrajOut(None, None, None, None, _ptr(traj['reward']), _ptr(traj['done']), None)
+        with torch.cuda.device(self.device):
+            _abi.check(self._policy_fn('cs_payoff_sums')(self._h, int(T), C.byref(tr), int(quota),
+                                                         _ptr(acc['games_per_env']), _ptr(acc['sums']),
+                                                         _ptr(acc['games']), self._stream()), 'cs_payoff_sums')
+        return acc
 
     # -- after the rollout (SURVEY 8(f)) ----------------------------------------------------------------------------
     def transitions(self, traj):
