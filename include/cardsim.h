@@ -70,8 +70,9 @@ typedef struct {
 /* cs_game_info grows at its end between ABI versions (2: game_words, deal_queue_depth, envs_per_wave; 3 adds the
  * cs_state_* functions); a consumer built against this header checks cs_abi_version() >= CS_ABI_VERSION before
  * calling cs_game_info_get, which writes sizeof(cs_game_info) bytes of this version. Functions added without a
- * layout change keep the version (cs_rollout_policy, cs_policy_actions, cs_payoff_sums): a consumer that may meet an
- * older library looks the symbol up. */
+ * layout change keep the version (cs_rollout_policy, cs_policy_actions, cs_payoff_sums; cs_qnet_values,
+ * cs_qnet_actions, the cs_replay_* functions, cs_dqn_targets): a consumer that may meet an older library looks the
+ * symbol up. */
 #define CS_ABI_VERSION 3
 
 /* Outputs of reset/step/observe, all device pointers, one row per env:
@@ -293,6 +294,76 @@ int cs_dmc_layer1(cs_handle* h, const float* X, const int32_t* state_of, const i
  * keyed by seed on (state_base + s, t) in place of np.random). actions int32 [S], -1 where a state has no entry. */
 int cs_dmc_select(const float* values, const int32_t* counts, const int64_t* offsets, const int32_t* ids, int64_t S,
                   float eps, uint64_t seed, uint64_t t, uint64_t state_base, int32_t* actions, void* stream);
+
+/* ---- DQN agent (rlcard/agents/dqn_agent.py) ---------------------------------------------------------------------
+ * Q-network of the agent as the kernels take it: a plain Linear/tanh stack, x -> tanh(W[0] x + b[0]) -> ... ->
+ * W[num_hidden] x + b[num_hidden]. The caller folds the eval-mode BatchNorm1d that precedes the first Linear in
+ * EstimatorNetwork into W[0] / b[0] (rlcard_amd.agents.Estimator.folded()). All pointers DEVICE memory, fp32. */
+enum { CS_QNET_MAX_HIDDEN = 4, CS_QNET_MAX_WIDTH = 128 };
+typedef struct {
+    int32_t in_dim;        /* = cs_game_info.obs_dim */
+    int32_t num_hidden;    /* 1..4 tanh layers */
+    int32_t hidden[4];     /* widths, each 1..128 */
+    int32_t num_actions;   /* = cs_game_info.num_actions, <= 8 */
+    int32_t reserved;
+    const float* W[5];     /* W[k] [out_k][in_k] row-major (torch Linear.weight), W[num_hidden] = output layer */
+    const float* b[5];
+} cs_qnet;
+
+/* DQNAgent.predict for `rows` observation rows: obs u8 [rows][obs_dim], legal u8 [rows][legal_bytes] or NULL (every
+ * action legal) -> q f32 [rows][num_actions], -inf where the action is illegal. Refusals (both functions): a game with
+ * more than 8 actions CS_E_UNSUPPORTED (DouDizhu), so is a net whose activations need more than 64 KB of LDS per 64 rows
+ * (max(in_dim, hidden[1], hidden[3]) + max(hidden[0], hidden[2]) above 256: two 128-wide layers are the largest);
+ * in_dim / num_actions not the handle's game's, widths or layer counts out of range, null weights
+ * CS_E_INVALID. */
+int cs_qnet_values(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* q,
+                   void* stream);
+/* DQNAgent.step / eval_step for `rows` rows: actions i32 [rows] = the first maximum of the row's Q-values among its
+ * legal actions, or with probability eps a uniform legal action -- cs_dmc_select's draw: Philox keyed by seed on
+ * (row_base + row, t), u = (r[0] >> 8) * 2^-24 < eps picks the ((r[1] * count) >> 32)-th legal action -- which has the
+ * distribution of DQNAgent.step's eps / len + (1 - eps) on the best action. A row whose done byte is set (done u8
+ * [rows], may be NULL) or whose legal mask is empty gets -1, cs_policy_actions' convention (cs_step ignores that
+ * action). q (may be NULL) takes cs_qnet_values' rows. */
+int cs_qnet_actions(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, const void* done,
+                    int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
+                    void* stream);
+
+/* Replay memory of a handle's envs on the device (dqn_agent.py Memory: a FIFO of `capacity` transitions [state,
+ * action, reward, next_state, done] plus the next state's legal mask). Each slot holds state and next_state u8
+ * [obs_dim], next_legal u8 [legal_bytes], action i32, reward f32, done u8. Games with a legal mask longer than 16
+ * bytes (DouDizhu) are CS_E_UNSUPPORTED. */
+typedef struct cs_replay cs_replay;
+/* cs_replay_gather outputs, DEVICE pointers (any may be NULL): state / next_state f32 [B][obs_dim] (the u8 -> f32
+ * conversion is fused), action i64 [B], reward f32 [B], next_legal u8 [B][legal_bytes], done u8 [B] */
+typedef struct { void *state, *action, *reward, *next_state, *next_legal, *done; } cs_replay_batch;
+int  cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out);
+void cs_replay_destroy(cs_replay* r);
+/* reorganize (rlcard/utils/utils.py:153-179) of a trajectory window of this handle (cs_rollout layout [T][n], every
+ * tensor including final_obs) for the seats in seat_mask (bit p = seat p). Row (t, e) with acting seat p: state =
+ * obs[t][e], next_state = obs[next_t][e] with its legal row, or, where the game ended first, final_obs[end_t][e][p],
+ * next_legal = 0, done = 1, reward = the seat's payoff. Rows with player >= num_players are not transitions. A row
+ * whose seat neither acts again nor sees its game end inside the window is kept pending (at most one per (env, seat))
+ * and completed by a later push -- by that seat's next row or by the game's end there, whatever that push's seat_mask.
+ * Order, the FIFO's: a push appends first the pending transitions it completes, in (env, seat) order, then its own
+ * completed rows in (t, env) order; positions come from a prefix sum. Of a push that yields more than `capacity`
+ * transitions only the last `capacity` are written. */
+int  cs_replay_push(cs_replay* r, int32_t T, const cs_traj_out* traj, uint32_t seat_mask, void* stream);
+/* Forget the pending rows (after a reset or re-seed of the envs: their games are gone). */
+int  cs_replay_drop_pending(cs_replay* r, void* stream);
+/* total = transitions ever appended, size = min(total, capacity). HOST out, synchronous. */
+int  cs_replay_size(cs_replay* r, int64_t* size, int64_t* total);
+/* Memory.sample's stacking: idx i64 [B] (DEVICE), idx[k] in [0, size) = the k-th OLDEST transition held (the
+ * reference's list index). An index outside that range is the caller's error (the kernel clamps it). B <= 0: no-op. */
+int  cs_replay_gather(cs_replay* r, const int64_t* idx, int64_t B, const cs_replay_batch* out, void* stream);
+
+/* Double-DQN targets (dqn_agent.py:205-218), all DEVICE: q_next / q_next_target f32 [B][num_actions], next_legal u8
+ * [B][ceil(num_actions / 8)], reward f32 [B], done u8 [B] -> best i32 [B] = the first maximum of q_next[b] over the
+ * legal actions (0 if none is legal: np.argmax of an all -inf row), target f32 [B] = reward[b] + (done[b] ? 0 : gamma)
+ * * q_next_target[b][best[b]], the product and the sum each rounded to fp32 (no FMA contraction): the reference's
+ * numpy line bit for bit. target or best may be NULL. */
+int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* next_legal, const float* reward,
+                   const void* done, int64_t B, int32_t num_actions, float gamma, float* target, int32_t* best,
+                   void* stream);
 
 /* Copy the packed state words of env `env` (state_words u32, HOST buffer) -- the raw fields behind
  * Env.get_state()['raw_obs'] / get_perfect_information for single-env compatibility and debugging. Synchronous.

@@ -7,6 +7,7 @@
 #include <string>
 #include "cs_engine.h"
 #include "cs_doudizhu.h"
+#include "cs_dqn.h"
 
 namespace cs {
 namespace ddz {
@@ -437,6 +438,183 @@ int cs_dmc_select(const float* values, const int32_t* counts, const int64_t* off
     hipError_t e = cs::launch_dmc_select(values, counts, offsets, ids, S, eps, seed, t, state_base, actions,
                                          (hipStream_t)stream);
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_select");
+}
+
+// ---- DQN ----------------------------------------------------------------------------------------------------------
+static int qnet_check(const cs_handle* h, const cs_qnet* net, const void* obs, int64_t rows)
+{
+    if (!h || !net || !obs) return fail(CS_E_INVALID, "null argument");
+    const cs_game_info& info = h->ops->info;
+    if (info.num_actions > 8) return fail(CS_E_UNSUPPORTED, "the Q-network kernel takes games of at most 8 actions");
+    if (net->in_dim != info.obs_dim || net->num_actions != info.num_actions)
+        return fail(CS_E_INVALID, "cs_qnet: in_dim / num_actions are not the handle's game's");
+    if (net->num_hidden < 1 || net->num_hidden > CS_QNET_MAX_HIDDEN)
+        return fail(CS_E_INVALID, "cs_qnet: num_hidden must be 1..4");
+    for (int l = 0; l <= net->num_hidden; l++) {
+        if (l < net->num_hidden && (net->hidden[l] < 1 || net->hidden[l] > CS_QNET_MAX_WIDTH))
+            return fail(CS_E_INVALID, "cs_qnet: hidden widths must be 1..128");
+        if (!net->W[l] || !net->b[l]) return fail(CS_E_INVALID, "cs_qnet: null weights");
+    }
+    if (cs::qnet_lds_bytes(*net) > 65536 + 2 * 4352)   // (64 KB of activations: two 128-wide layers, and two weight tiles)
+        return fail(CS_E_UNSUPPORTED, "cs_qnet: the net's activations need more than 64 KB of LDS per 64 rows");
+    if (rows < 0 || rows > 0x7FFFFFFF) return fail(CS_E_INVALID, "rows out of range");
+    return CS_OK;
+}
+
+int cs_qnet_values(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* q,
+                   void* stream)
+{
+    int r = qnet_check(h, net, obs, rows);
+    if (r != CS_OK) return r;
+    if (!q) return fail(CS_E_INVALID, "null argument");
+    if (rows == 0) return CS_OK;
+    if ((r = set_device(h)) != CS_OK) return r;
+    hipError_t e = cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0.f, 0, 0, 0,
+                                   nullptr, q, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_qnet_values");
+}
+
+int cs_qnet_actions(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, const void* done,
+                    int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
+                    void* stream)
+{
+    int r = qnet_check(h, net, obs, rows);
+    if (r != CS_OK) return r;
+    if (!actions) return fail(CS_E_INVALID, "null argument");
+    if (rows == 0) return CS_OK;
+    if ((r = set_device(h)) != CS_OK) return r;
+    hipError_t e = cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done, rows, eps,
+                                   seed, t, row_base, actions, q, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_qnet_actions");
+}
+
+struct cs_replay {
+    cs_handle* h;
+    cs::ReplayRing r;
+    void* mem;          // one allocation for the ring, the pending store and the counter
+    int32_t* scratch;   // code and pos of a push, [2][entries] (grown on demand)
+    int64_t entries;
+    void* scan_tmp;
+    size_t scan_bytes;
+};
+
+int cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out)
+{
+    if (!h || !out) return fail(CS_E_INVALID, "null argument");
+    *out = nullptr;
+    if (capacity <= 0) return fail(CS_E_INVALID, "capacity must be positive");
+    const cs_game_info& info = h->ops->info;
+    if (info.legal_bytes > 16) return fail(CS_E_UNSUPPORTED, "cs_replay: legal masks of at most 16 bytes");
+    int r = set_device(h);
+    if (r != CS_OK) return r;
+    const int64_t O = info.obs_dim, LB = info.legal_bytes, NP = h->b.n * info.num_players, cap = capacity;
+    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
+    const int64_t o_st = 0, o_nst = o_st + al(cap * O), o_nlg = o_nst + al(cap * O), o_act = o_nlg + al(cap * LB),
+                  o_rew = o_act + al(cap * 4), o_dne = o_rew + al(cap * 4), o_pst = o_dne + al(cap),
+                  o_pact = o_pst + al(NP * O), o_np = o_pact + al(NP * 4), o_pv = o_np + al(NP * 4),
+                  o_tot = o_pv + al(NP), total = o_tot + 256;
+    cs_replay* p = new (std::nothrow) cs_replay();
+    if (!p) return fail(CS_E_INVALID, "out of host memory");
+    hipError_t e = hipMalloc(&p->mem, (size_t)total);
+    if (e != hipSuccess) { delete p; return fail_hip(e, "cs_replay_create"); }
+    uint8_t* m = (uint8_t*)p->mem;
+    // no pending rows, nothing appended; the slots are written before they are read
+    e = hipMemset(m + o_pv, 0, (size_t)(total - o_pv));
+    if (e != hipSuccess) { (void)hipFree(p->mem); delete p; return fail_hip(e, "cs_replay_create"); }
+    p->h = h;
+    p->r = cs::ReplayRing{cap, (int32_t)O, (int32_t)LB, info.num_players, info.action_bytes, m + o_st, m + o_nst,
+                          m + o_nlg, (int32_t*)(m + o_act), (float*)(m + o_rew), m + o_dne, (int64_t*)(m + o_tot),
+                          m + o_pv, m + o_pst, (int32_t*)(m + o_pact), (int32_t*)(m + o_np)};
+    p->scratch = nullptr;
+    p->entries = 0;
+    p->scan_tmp = nullptr;
+    p->scan_bytes = 0;
+    *out = p;
+    return CS_OK;
+}
+
+void cs_replay_destroy(cs_replay* r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->h->device);
+    if (r->mem) (void)hipFree(r->mem);
+    if (r->scratch) (void)hipFree(r->scratch);
+    if (r->scan_tmp) (void)hipFree(r->scan_tmp);
+    delete r;
+}
+
+int cs_replay_push(cs_replay* r, int32_t T, const cs_traj_out* traj, uint32_t seat_mask, void* stream)
+{
+    if (!r || !traj) return fail(CS_E_INVALID, "null argument");
+    if (!traj->obs || !traj->legal || !traj->player || !traj->action || !traj->reward || !traj->done ||
+        !traj->final_obs)
+        return fail(CS_E_INVALID, "cs_replay_push needs every trajectory buffer, final_obs included");
+    if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
+    const int64_t entries = r->h->b.n * r->r.P + (int64_t)T * r->h->b.n + 1;
+    if (entries > 0x7FFFFFFF) return fail(CS_E_INVALID, "cs_replay_push: window too large (T * n must stay below 2^31)");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    if (entries > r->entries) {
+        if (r->scratch) (void)hipFree(r->scratch);
+        r->scratch = nullptr;
+        r->entries = 0;
+        hipError_t e = hipMalloc((void**)&r->scratch, (size_t)entries * 2 * sizeof(int32_t));
+        if (e != hipSuccess) return fail_hip(e, "cs_replay_push");
+        r->entries = entries;
+    }
+    hipError_t e = cs::launch_replay_push(r->h->b, r->r, T, *traj, seat_mask, r->scratch, r->scratch + r->entries,
+                                          &r->scan_tmp, &r->scan_bytes, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_push");
+}
+
+int cs_replay_drop_pending(cs_replay* r, void* stream)
+{
+    if (!r) return fail(CS_E_INVALID, "null argument");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    hipError_t e = hipMemsetAsync(r->r.pvalid, 0, (size_t)(r->h->b.n * r->r.P), (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_drop_pending");
+}
+
+int cs_replay_size(cs_replay* r, int64_t* size, int64_t* total)
+{
+    if (!r || (!size && !total)) return fail(CS_E_INVALID, "null argument");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    int64_t t = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&t, r->r.total, sizeof(int64_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, "cs_replay_size");
+    if (total) *total = t;
+    if (size) *size = t < r->r.cap ? t : r->r.cap;
+    return CS_OK;
+}
+
+int cs_replay_gather(cs_replay* r, const int64_t* idx, int64_t B, const cs_replay_batch* out, void* stream)
+{
+    if (!r || !out) return fail(CS_E_INVALID, "null argument");
+    if (B <= 0) return CS_OK;
+    if (!idx) return fail(CS_E_INVALID, "null argument");
+    if (B > 0x7FFFFFFF / 32) return fail(CS_E_INVALID, "B out of range");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    hipError_t e = cs::launch_replay_gather(r->r, idx, B, *out, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_gather");
+}
+
+int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* next_legal, const float* reward,
+                   const void* done, int64_t B, int32_t num_actions, float gamma, float* target, int32_t* best,
+                   void* stream)
+{
+    if (!q_next || !next_legal || (!target && !best)) return fail(CS_E_INVALID, "null argument");
+    if (target && (!q_next_target || !reward || !done)) return fail(CS_E_INVALID, "null argument");
+    if (num_actions <= 0) return fail(CS_E_INVALID, "num_actions must be positive");
+    if (B < 0 || B > 0x7FFFFFFF) return fail(CS_E_INVALID, "B out of range");
+    if (B == 0) return CS_OK;
+    hipError_t e = cs::launch_dqn_targets(q_next, q_next_target, (const uint8_t*)next_legal, reward,
+                                          (const uint8_t*)done, B, num_actions, gamma, target, best,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dqn_targets");
 }
 
 int cs_traj_probe(cs_handle* h, int32_t T, const cs_traj_out* out, void* stream)

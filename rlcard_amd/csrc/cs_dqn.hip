@@ -1,0 +1,482 @@
+// cs_dqn.hip -- the DQN agent's device side (rlcard/agents/dqn_agent.py), for every env of a handle at once:
+//
+//   k_qnet            DQNAgent.predict / step / eval_step: the Q-network (eval-mode BatchNorm folded into the first
+//                     Linear by the caller, then Linear/tanh layers and the output Linear) for 64 obs rows per block,
+//                     masked by the legal bitmask, with the first-maximum argmax and k_dmc_select's epsilon draw fused
+//                     in. fp32 FMAs with fp32 accumulation in input-unit order, no MFMA (fp32 MFMA runs at the vector
+//                     rate on gfx950, and bf16 would cost the fp32 agreement with the torch network).
+//                       layout: the block's activations live in LDS, transposed [unit][row], two buffers (in and out of
+//                       a layer, swapped per layer) sized by the widths they hold. A hidden layer is computed in tiles
+//                       of 64 rows x 64 output units by one wave, each lane an 8 x 8 register tile: per input unit two
+//                       16-B LDS reads of 8 activations and two of 8 weights feed 64 FMAs, so neither the LDS pipe nor
+//                       a load's latency bounds the loop (a first version with one row per lane, 8 outputs per
+//                       activation read and the weights by scalar loads waited on the scalar cache: 1.37 ms for 2^20
+//                       Leduc rows against this one's 0.64, profiles/EXPERIMENTS.md D-1). The weights of a tile come
+//                       through a per-wave LDS stage of 16 input units, loaded coalesced (16 lanes per weight row) into
+//                       registers while the previous stage's FMAs run. A net with a layer wider than 64 units runs two
+//                       waves per block, one per tile of the layer. The output layer (<= 8 actions) is one pass with a
+//                       lane per row, its weights staged once, and stays in registers for the mask and the argmax.
+//   k_replay_index / k_replay_write / k_replay_carry
+//                     reorganize (rlcard/utils/utils.py:153-179) of a trajectory window into the replay ring, with the
+//                     rows whose game runs past the window carried as one pending row per (env, seat) and completed by
+//                     a later push. Write positions come from one prefix sum over [pending (env, seat)] + [rows (t, env)].
+//   k_replay_gather   Memory.sample's stacking, u8 -> f32 fused.
+//   k_dqn_targets     dqn_agent.py:205-218: Double-DQN best next action and target, each operation rounded to fp32.
+#include <hipcub/hipcub.hpp>
+#include <math.h>
+#include "cs_device.h"
+#include "cs_dqn.h"
+
+namespace cs {
+
+constexpr int QOC = 8;        // the most actions k_qnet takes: the output layer is one register pass of 8 units
+constexpr int QROWS = 64;     // rows per block of k_qnet: one wave, or two that split a layer's 64-unit tiles
+constexpr int QKT = 16;       // input units per staged weight tile
+constexpr int QWS = 68;       // floats per input unit in the weight tile: 64 output units + 4 (16-B aligned rows whose
+                              // 16 staging lanes of one output unit land on different banks)
+constexpr int QWT = QKT * QWS;   // floats of the weight tile (the output layer's [in <= 128][8] image fits too)
+constexpr int QBLOCK = 256;   // block of the streaming kernels
+constexpr int QMAXP = 10;     // players per env (cs_traj.hip MAXP)
+
+// weights W[ot + o][kt + k], o < 64, k < QKT, of one tile into registers: element lane + 64 s is (o, k) = (that >> 4,
+// that & 15), so 16 consecutive lanes read 64 consecutive bytes of one weight row; zeros past the matrix
+__device__ __forceinline__ void qnet_tile_load(const float* __restrict__ W, int in, int out, int ot, int kt, int lane,
+                                               float (&pre)[QKT])
+{
+#pragma unroll
+    for (int s = 0; s < QKT; s++) {
+        const int idx = lane + 64 * s, o = ot + (idx >> 4), k = kt + (idx & 15);
+        pre[s] = (o < out && k < in) ? W[(int64_t)o * in + k] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, int szB, const uint8_t* __restrict__ obs,
+                                                const uint8_t* __restrict__ legal, const uint8_t* __restrict__ done,
+                                                int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base,
+                                                int32_t* __restrict__ actions, float* __restrict__ q)
+{
+    extern __shared__ __attribute__((aligned(16))) float q_lds[];
+    const int tid = (int)threadIdx.x, BT = (int)blockDim.x, lane = tid & (WAVE - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), NW = BT >> 6;   // this wave of the block's 1 or 2
+    const int64_t row0 = (int64_t)blockIdx.x * QROWS, row = row0 + lane;
+    const int D = net.in_dim, A = net.num_actions, NH = net.num_hidden;
+    float* bufA = q_lds;                  // [szA][64]: the obs rows, then the outputs of layers 1, 3
+    float* bufB = bufA + szA * QROWS;     // [szB][64]: the outputs of layers 0, 2
+    float* wt0 = bufB + szB * QROWS;      // [NW][QKT][QWS]: a weight tile per wave, input-unit major
+    float* wt = wt0 + wv * QWT;
+    {   // obs rows of the block -> bufA as floats: consecutive lanes, consecutive bytes
+        const int64_t left = rows - row0;
+        const int nb = (int)(left < QROWS ? left : QROWS) * D;
+        const uint8_t* src = obs + row0 * D;
+        for (int j = tid; j < nb; j += BT) {
+            const int r = j / D, u = j - r * D;
+            bufA[u * QROWS + r] = (float)src[j];
+        }
+    }
+    const int lr = lane & 7, lo = lane >> 3;   // the lane's 8 rows (8 lr ..) and 8 output units (8 lo ..) of a tile
+    float* xin = bufA;
+    float* xout = bufB;
+    int in = D;
+    for (int l = 0; l < NH; l++) {
+        const int out = net.hidden[l];
+        const float* __restrict__ W = net.W[l];
+        const float* __restrict__ bias = net.b[l];
+        for (int ot0 = 0; ot0 < out; ot0 += 64 * NW) {   // (every wave passes the barriers; one without a tile idles)
+            const int ot = ot0 + 64 * wv;
+            const bool mine = ot < out;
+            float acc[8][8];   // [output unit][row]
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int o = ot + lo * 8 + j;
+                const float b = bias[o < out ? o : out - 1];
+#pragma unroll
+                for (int i = 0; i < 8; i++) acc[j][i] = b;
+            }
+            float pre[QKT];
+            if (mine) qnet_tile_load(W, in, out, ot, 0, lane, pre);
+            for (int kt = 0; kt < in; kt += QKT) {
+                __syncthreads();   // the tile's readers (and, first, the writers of xin) are done
+                if (mine) {
+#pragma unroll
+                    for (int s = 0; s < QKT; s++) {
+                        const int idx = lane + 64 * s;
+                        wt[(idx & 15) * QWS + (idx >> 4)] = pre[s];
+                    }
+                }
+                __syncthreads();
+                if (!mine) continue;
+                if (kt + QKT < in) qnet_tile_load(W, in, out, ot, kt + QKT, lane, pre);   // in flight under the FMAs
+                const int kn = in - kt < QKT ? in - kt : QKT;
+#pragma unroll 2
+                for (int k = 0; k < kn; k++) {
+                    const float4 a0 = *(const float4*)(xin + (kt + k) * QROWS + lr * 8);
+                    const float4 a1 = *(const float4*)(xin + (kt + k) * QROWS + lr * 8 + 4);
+                    const float4 w0 = *(const float4*)(wt + k * QWS + lo * 8);
+                    const float4 w1 = *(const float4*)(wt + k * QWS + lo * 8 + 4);
+                    const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                    const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+                    for (int j = 0; j < 8; j++)
+#pragma unroll
+                        for (int i = 0; i < 8; i++) acc[j][i] = fmaf(w[j], a[i], acc[j][i]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int o = ot + lo * 8 + j;
+                if (o < out) {
+                    float* d = xout + o * QROWS + lr * 8;
+                    *(float4*)d = make_float4(tanhf(acc[j][0]), tanhf(acc[j][1]), tanhf(acc[j][2]), tanhf(acc[j][3]));
+                    *(float4*)(d + 4) =
+                        make_float4(tanhf(acc[j][4]), tanhf(acc[j][5]), tanhf(acc[j][6]), tanhf(acc[j][7]));
+                }
+            }
+        }
+        float* nx = xin;
+        xin = xout;
+        xout = nx;
+        in = out;
+    }
+    // output layer, one lane per row: its weights as wt[k][8] (zeros past A), read back as two broadcast float4
+    __syncthreads();
+    {
+        const float* __restrict__ W = net.W[NH];
+        for (int idx = tid; idx < in * QOC; idx += BT) {
+            const int k = idx >> 3, a = idx & 7;
+            wt0[idx] = a < A ? W[(int64_t)a * in + k] : 0.f;
+        }
+    }
+    __syncthreads();
+    if (wv != 0) return;
+    float acc[QOC];
+#pragma unroll
+    for (int k = 0; k < QOC; k++) acc[k] = net.b[NH][k < A ? k : A - 1];
+    for (int k = 0; k < in; k++) {
+        const float x = xin[k * QROWS + lane];
+        const float4 w0 = *(const float4*)(wt0 + k * QOC), w1 = *(const float4*)(wt0 + k * QOC + 4);
+        const float w[QOC] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+        for (int j = 0; j < QOC; j++) acc[j] = fmaf(w[j], x, acc[j]);
+    }
+    if (row >= rows) return;
+    const uint32_t all = (1u << A) - 1u;
+    const uint32_t mask = legal ? (uint32_t)legal[row] & all : all;   // A <= 8: one mask byte per row
+    if (q) {
+#pragma unroll
+        for (int k = 0; k < QOC; k++)
+            if (k < A) q[row * A + k] = (mask >> k) & 1u ? acc[k] : -INFINITY;
+    }
+    if (!actions) return;
+    int best = -1;
+    float bv = 0.f;
+#pragma unroll
+    for (int k = 0; k < QOC; k++)
+        if (((mask >> k) & 1u) && (best < 0 || acc[k] > bv)) {
+            best = k;
+            bv = acc[k];
+        }
+    if (best >= 0 && eps > 0.f) {   // k_dmc_select's draw (cs_dmc.hip)
+        uint32_t r[4];
+        philox4(seed, row_base + (uint64_t)row, t, r);
+        const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+        if (u < eps) {
+            int kth = (int)(((uint64_t)r[1] * (uint64_t)__popc(mask)) >> 32);
+            uint32_t m = mask;
+            while (kth-- > 0) m &= m - 1;
+            best = __builtin_ctz(m);
+        }
+    }
+    if (done && done[row]) best = -1;
+    actions[row] = best;
+}
+
+static void qnet_sizes(const cs_qnet& net, int* szA, int* szB)
+{
+    int a = net.in_dim, b = 1;
+    for (int l = 0; l < net.num_hidden; l++) {
+        int& dst = (l & 1) ? a : b;
+        if (net.hidden[l] > dst) dst = net.hidden[l];
+    }
+    *szA = a;
+    *szB = b;
+}
+
+// waves of a k_qnet block: a second one where a layer is wider than one 64-unit tile
+static int qnet_waves(const cs_qnet& net)
+{
+    for (int l = 0; l < net.num_hidden; l++)
+        if (net.hidden[l] > 64) return 2;
+    return 1;
+}
+
+int64_t qnet_lds_bytes(const cs_qnet& net)
+{
+    int a, b;
+    qnet_sizes(net, &a, &b);
+    return (((int64_t)a + b) * QROWS + qnet_waves(net) * QWT) * (int64_t)sizeof(float);
+}
+
+hipError_t launch_qnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
+                       float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
+                       hipStream_t s)
+{
+    int szA, szB;
+    qnet_sizes(net, &szA, &szB);
+    const int64_t bytes = qnet_lds_bytes(net);
+    if (bytes > 65536) {   // past the default limit of dynamic LDS (the [128, 128, ..] nets): raise this kernel's
+        hipError_t e = hipFuncSetAttribute((const void*)k_qnet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_qnet, dim3((unsigned)((rows + QROWS - 1) / QROWS)), dim3(QROWS * qnet_waves(net)), (size_t)bytes, s, net, szA,
+                       szB, obs, legal, done, rows, eps, seed, t, row_base, actions, q);
+    return hipGetLastError();
+}
+
+// ---- replay ring ---------------------------------------------------------------------------------------------------
+// Codes of an entry (a pending (env, seat) or a trajectory row): >= 0 the row of the next state (obs[code][e]);
+// <= -3 the game ended first, at row -3 - code (final_obs there); -2 still running past the window; -1 not a transition.
+struct ReplayCount {
+    __host__ __device__ int32_t operator()(const int32_t& c) const { return (c >= 0 || c <= -3) ? 1 : 0; }
+};
+
+// One lane per env, its T rows scanned backwards (as k_transitions): code of every row of a seat in seat_mask, the
+// code that completes each seat's pending row (code[e * P + q]), and the row that becomes the seat's new pending row.
+__global__ __launch_bounds__(QBLOCK) void k_replay_index(const uint8_t* __restrict__ player,
+                                                         const uint8_t* __restrict__ done, int T, int64_t n, int P,
+                                                         uint32_t seat_mask, const uint8_t* __restrict__ pvalid,
+                                                         int32_t* __restrict__ code, int32_t* __restrict__ newpend)
+{
+    const int64_t e = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (e == 0) code[n * P + (int64_t)T * n] = -1;   // the scan's last entry: its exclusive sum is the push's total
+    if (e >= n) return;
+    int32_t nxt[QMAXP], np_[QMAXP];
+#pragma unroll
+    for (int k = 0; k < QMAXP; k++) {
+        nxt[k] = -2;
+        np_[k] = -1;
+    }
+    int32_t* rows = code + n * P;
+    for (int t = T - 1; t >= 0; t--) {
+        const int64_t row = (int64_t)t * n + e;
+        if (done[row]) {
+#pragma unroll
+            for (int k = 0; k < QMAXP; k++) nxt[k] = -3 - t;
+        }
+        const int p = player[row];
+        int32_t c = -1;
+#pragma unroll
+        for (int k = 0; k < QMAXP; k++) {
+            if (k == p && k < P) {
+                if ((seat_mask >> k) & 1u) {
+                    c = nxt[k];
+                    if (c == -2) np_[k] = t;
+                }
+                nxt[k] = t;
+            }
+        }
+        rows[row] = c;
+    }
+#pragma unroll
+    for (int k = 0; k < QMAXP; k++) {
+        if (k < P) {
+            code[e * P + k] = pvalid[e * P + k] ? nxt[k] : -1;
+            newpend[e * P + k] = np_[k];
+        }
+    }
+}
+
+// One thread per (entry, 4 obs bytes): entry j < n * P is the pending row of (env, seat) j, the others are the window's
+// rows. The entry's transition lands in slot (total + pos[j]) % cap; of a push with more than cap transitions only the
+// last cap are written, so no two entries share a slot.
+__global__ __launch_bounds__(QBLOCK) void k_replay_write(ReplayRing r, int T, int64_t n, const uint8_t* __restrict__ obs,
+                                                         const uint8_t* __restrict__ legal,
+                                                         const uint8_t* __restrict__ player,
+                                                         const void* __restrict__ action,
+                                                         const float* __restrict__ reward,
+                                                         const uint8_t* __restrict__ final_obs,
+                                                         const int32_t* __restrict__ code,
+                                                         const int32_t* __restrict__ pos)
+{
+    const int O = r.O, P = r.P, q4 = (O + 3) / 4;
+    const int64_t NP = n * P, M = NP + (int64_t)T * n;
+    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (i >= M * q4) return;
+    const int64_t j = i / q4;
+    const int c0 = (int)(i - j * q4) * 4;
+    const int32_t c = code[j];
+    if (!(c >= 0 || c <= -3)) return;
+    const int64_t fresh = pos[M], at = pos[j];
+    if (at < fresh - r.cap) return;
+    const int64_t slot = (*r.total + at) % r.cap;
+    int64_t e;
+    int p, a;
+    const uint8_t* s_src;
+    if (j < NP) {
+        e = j / P;
+        p = (int)(j - e * P);
+        s_src = r.pst + j * O;
+        a = r.pact[j];
+    } else {
+        const int64_t row = j - NP;
+        e = row % n;
+        p = player[row];
+        s_src = obs + row * O;
+        a = r.abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+    }
+    const bool ended = c < 0;
+    const int64_t nrow = (int64_t)(ended ? -3 - c : c) * n + e;
+    const uint8_t* n_src = ended ? final_obs + (nrow * P + p) * O : obs + nrow * O;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (c0 + k < O) {
+            r.st[slot * O + c0 + k] = s_src[c0 + k];
+            r.nst[slot * O + c0 + k] = n_src[c0 + k];
+        }
+    }
+    if (c0 == 0) {
+        r.act[slot] = a;
+        r.rew[slot] = ended ? reward[nrow * P + p] : 0.f;
+        r.dne[slot] = ended ? 1 : 0;
+        for (int k = 0; k < r.LB; k++) r.nlg[slot * r.LB + k] = ended ? (uint8_t)0 : legal[nrow * r.LB + k];
+    }
+}
+
+// After the write: the rows that stay pending move into the (env, seat) pending store (one thread per (env, seat, 4 obs
+// bytes)), completed ones are cleared, and the ring's total advances by the push's count.
+__global__ __launch_bounds__(QBLOCK) void k_replay_carry(ReplayRing r, int T, int64_t n, const uint8_t* __restrict__ obs,
+                                                         const void* __restrict__ action,
+                                                         const int32_t* __restrict__ code,
+                                                         const int32_t* __restrict__ pos)
+{
+    const int O = r.O, q4 = (O + 3) / 4;
+    const int64_t NP = n * r.P;
+    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (i == 0) *r.total += pos[NP + (int64_t)T * n];
+    if (i >= NP * q4) return;
+    const int64_t j = i / q4;
+    const int c0 = (int)(i - j * q4) * 4;
+    const int32_t t = r.newpend[j];
+    if (t < 0) {
+        const int32_t c = code[j];
+        if (c0 == 0 && (c >= 0 || c <= -3)) r.pvalid[j] = 0;
+        return;
+    }
+    const int64_t row = (int64_t)t * n + j / r.P;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (c0 + k < O) r.pst[j * O + c0 + k] = obs[row * O + c0 + k];
+    if (c0 == 0) {
+        r.pact[j] = r.abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+        r.pvalid[j] = 1;
+    }
+}
+
+hipError_t launch_replay_push(const Buffers& b, const ReplayRing& r, int32_t T, const cs_traj_out& tr,
+                              uint32_t seat_mask, int32_t* code, int32_t* pos, void** tmp, size_t* tmp_bytes,
+                              hipStream_t s)
+{
+    const int64_t n = b.n, NP = n * r.P, M = NP + (int64_t)T * n;
+    const int q4 = (r.O + 3) / 4;
+    hipLaunchKernelGGL(k_replay_index, dim3((unsigned)((n + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s,
+                       (const uint8_t*)tr.player, (const uint8_t*)tr.done, T, n, r.P, seat_mask, r.pvalid, code,
+                       r.newpend);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipcub::TransformInputIterator<int32_t, ReplayCount, const int32_t*> counts(code, ReplayCount());
+    size_t need = 0;
+    if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, pos, (int)(M + 1), s)) != hipSuccess) return e;
+    if (need > *tmp_bytes) {
+        if (*tmp) (void)hipFree(*tmp);
+        *tmp = nullptr;
+        *tmp_bytes = 0;
+        if ((e = hipMalloc(tmp, need)) != hipSuccess) return e;
+        *tmp_bytes = need;
+    }
+    if ((e = hipcub::DeviceScan::ExclusiveSum(*tmp, need, counts, pos, (int)(M + 1), s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_replay_write, dim3((unsigned)((M * q4 + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, r, T, n,
+                       (const uint8_t*)tr.obs, (const uint8_t*)tr.legal, (const uint8_t*)tr.player, tr.action,
+                       (const float*)tr.reward, (const uint8_t*)tr.final_obs, code, pos);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_replay_carry, dim3((unsigned)((NP * q4 + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, r, T, n,
+                       (const uint8_t*)tr.obs, tr.action, code, pos);
+    return hipGetLastError();
+}
+
+// idx[k] = the k-th oldest transition held: slot (total - size + idx[k]) % cap. One thread per (k, 4 obs units). An
+// index outside [0, size) is the caller's error; it is clamped, so the kernel reads inside the ring whatever it is.
+__global__ __launch_bounds__(QBLOCK) void k_replay_gather(ReplayRing r, const int64_t* __restrict__ idx, int64_t B,
+                                                          float* o_st, int64_t* o_act, float* o_rew, float* o_nst,
+                                                          uint8_t* o_nlg, uint8_t* o_dne)
+{
+    const int O = r.O, q4 = (O + 3) / 4;
+    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (i >= B * q4) return;
+    const int64_t k = i / q4;
+    const int c0 = (int)(i - k * q4) * 4;
+    const int64_t total = *r.total, size = total < r.cap ? total : r.cap;
+    int64_t x = idx[k];
+    x = x < 0 ? 0 : (x >= size ? (size > 0 ? size - 1 : 0) : x);
+    const int64_t slot = (total - size + x) % r.cap;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        if (c0 + u < O) {
+            if (o_st) o_st[k * O + c0 + u] = (float)r.st[slot * O + c0 + u];
+            if (o_nst) o_nst[k * O + c0 + u] = (float)r.nst[slot * O + c0 + u];
+        }
+    }
+    if (c0 == 0) {
+        if (o_act) o_act[k] = r.act[slot];
+        if (o_rew) o_rew[k] = r.rew[slot];
+        if (o_dne) o_dne[k] = r.dne[slot];
+        if (o_nlg)
+            for (int u = 0; u < r.LB; u++) o_nlg[k * r.LB + u] = r.nlg[slot * r.LB + u];
+    }
+}
+
+hipError_t launch_replay_gather(const ReplayRing& r, const int64_t* idx, int64_t B, const cs_replay_batch& o,
+                                hipStream_t s)
+{
+    const int64_t work = B * ((r.O + 3) / 4);
+    hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)((work + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, r, idx, B,
+                       (float*)o.state, (int64_t*)o.action, (float*)o.reward, (float*)o.next_state,
+                       (uint8_t*)o.next_legal, (uint8_t*)o.done);
+    return hipGetLastError();
+}
+
+// ---- Double-DQN targets ----------------------------------------------------------------------------------------------
+// best = first maximum of q_next over the legal actions (0 when none is legal: np.argmax of an all -inf row);
+// target = reward + (done ? 0 : gamma) * q_next_target[best], the product and the sum each rounded to fp32.
+__global__ __launch_bounds__(QBLOCK) void k_dqn_targets(const float* __restrict__ qn, const float* __restrict__ qt,
+                                                        const uint8_t* __restrict__ next_legal,
+                                                        const float* __restrict__ reward,
+                                                        const uint8_t* __restrict__ done, int64_t B, int A, int LB,
+                                                        float gamma, float* target, int32_t* best)
+{
+    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (i >= B) return;
+    int bi = -1;
+    float bv = 0.f;
+    for (int a = 0; a < A; a++) {
+        if ((next_legal[i * LB + (a >> 3)] >> (a & 7)) & 1) {
+            const float v = qn[i * A + a];
+            if (bi < 0 || v > bv) {
+                bi = a;
+                bv = v;
+            }
+        }
+    }
+    if (bi < 0) bi = 0;
+    if (best) best[i] = bi;
+    if (target) target[i] = __fadd_rn(reward[i], __fmul_rn(done[i] ? 0.f : gamma, qt[i * A + bi]));
+}
+
+hipError_t launch_dqn_targets(const float* q_next, const float* q_next_target, const uint8_t* next_legal,
+                              const float* reward, const uint8_t* done, int64_t B, int32_t A, float gamma,
+                              float* target, int32_t* best, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_dqn_targets, dim3((unsigned)((B + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, q_next,
+                       q_next_target, next_legal, reward, done, B, A, (A + 7) / 8, gamma, target, best);
+    return hipGetLastError();
+}
+
+}  // namespace cs

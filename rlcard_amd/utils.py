@@ -66,20 +66,50 @@ def tournament_vec(vec_env, policies, games_per_env, T=64, policy_seed=0):
     payoff per seat over exactly the first games_per_env games of every env, as a list. The payoffs are summed on the
     device (VecEnv.payoff_sums); the host reads back one scalar per window, the smallest per-env game count. Counting
     each env's first games, not the games finished when the last window ends, keeps short games from being favoured
-    and makes the result independent of T."""
+    and makes the result independent of T.
+    A seat may also be an object with eval_step_vec(state, t) -> int32 [N] actions (a DQNAgent attached to vec_env: its
+    Q-network on the device). Then the envs are stepped: each step, every env takes the action of its acting seat --
+    eval_step_vec for such a seat, VecEnv.policy_actions for an engine policy -- and the rewards and done flags of T
+    steps go through the same payoff_sums with the same quota. With engine policies only, the fused rollout runs."""
     quota = int(games_per_env)
     if quota <= 0:
         raise ValueError('games_per_env must be positive')
     traj = vec_env.new_traj_out(T, select=1)
     acc = vec_env.new_payoff_sums()
+    stepped = any(hasattr(p, 'eval_step_vec') for p in policies)
+    if stepped and len(policies) != vec_env.num_players:
+        raise ValueError('expected %d policies (one per seat), got %d' % (vec_env.num_players, len(policies)))
+    state = vec_env.reset() if stepped else None
     t0 = 0
     while True:
-        vec_env.rollout(T, policy_seed=policy_seed, t0=t0, out=traj, policies=policies)
+        if stepped:
+            state = _tournament_steps(vec_env, policies, state, traj, T, policy_seed, t0)
+        else:
+            vec_env.rollout(T, policy_seed=policy_seed, t0=t0, out=traj, policies=policies)
         vec_env.payoff_sums(traj, acc, quota)
         t0 += T
         if int(acc['games_per_env'].min().item()) >= quota:
             break
     return list((acc['sums'] / acc['games'].to(acc['sums'].dtype)).cpu().numpy())
+
+
+def _tournament_steps(vec_env, policies, state, traj, T, policy_seed, t0):
+    """T single steps of tournament_vec's stepped form from `state`, their rewards and done flags into traj -> the
+    state after them. A finished env's next step starts its next game (lazy auto-reset: reward 0, done 0)."""
+    import torch
+    for k in range(T):
+        player = state['player'].long()
+        acts = None
+        for p, pol in enumerate(policies):
+            if hasattr(pol, 'eval_step_vec'):
+                a = pol.eval_step_vec(state, t0 + k)
+            else:
+                a = vec_env.policy_actions(pol, policy_seed, t0 + k)
+            acts = a if acts is None else torch.where(player == p, a, acts)
+        state = vec_env.step(acts)
+        traj['reward'][k].copy_(state['reward'])
+        traj['done'][k].copy_(state['done'])
+    return state
 
 
 # ---- PettingZoo-side helpers (rlcard/utils/pettingzoo_utils.py:5-72) --------------------------------------------------
