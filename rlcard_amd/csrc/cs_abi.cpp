@@ -108,7 +108,7 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     h->b.dealer_id = cfg ? cfg->dealer_plus1 - 1 : -1;
     h->b.rng_mode = cfg ? cfg->rng_mode : CS_RNG_MT19937;
     h->b.rec = cs::StepRecord{nullptr, nullptr, 0u, 0};
-    h->b.serial_refill = 0;
+    h->b.kernel_flags = 0;
     h->b.table = nullptr;
     if (int r = set_device(h)) { delete h; return r; }
     const size_t n = (size_t)num_envs;
@@ -815,7 +815,7 @@ int cs_debug_ddz_legal(cs_handle* h, const uint8_t* counts, const int32_t* prev,
 int cs_debug_set_serial_refill(cs_handle* h, int32_t enable)
 {
     if (!h) return fail(CS_E_INVALID, "null argument");
-    h->b.serial_refill = (h->b.serial_refill & ~1) | (enable ? 1 : 0);
+    h->b.kernel_flags = (h->b.kernel_flags & ~1) | (enable ? 1 : 0);
     return CS_OK;
 }
 
@@ -823,7 +823,7 @@ int cs_debug_set_kernel_flags(cs_handle* h, int32_t flags)
 {
     if (!h) return fail(CS_E_INVALID, "null argument");
     if (flags < 0 || flags > 7) return fail(CS_E_INVALID, "unknown kernel flag bits");
-    h->b.serial_refill = flags;
+    h->b.kernel_flags = flags;
     return CS_OK;
 }
 

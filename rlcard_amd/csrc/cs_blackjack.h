@@ -30,23 +30,20 @@
 namespace cs {
 
 template <int NP>
-struct Blackjack {
+struct Blackjack : GameDefaults {
     static constexpr int OBS = 2, A = 2, P = NP, LB = 1, WORDS = 32, ACTION_BYTES = 1;
     static constexpr int NB = 1;               // raw obs dwords
-    static constexpr bool RING = true;          // MT stream as the byte ring (cs_ring.h)
     static constexpr bool RAW_OBS = true;      // observe() returns byte values, not a 0/1 bitmap
     static constexpr int HAND_CAP = 12;
     static constexpr int HAND_W = 3 * (NP + 1);                 // state words 15.. the hands use
     static constexpr int SCRATCH_WORDS = 3 + HAND_W > 13 ? 3 + HAND_W : 13;   // >= 13: the reset's deck bytes
-    // MT staging (see MtLaneT)
     // MT staging rows of 128 bytes: the reset's ~57 draws come out of one branch-free pass over them
     // (RingLane::draw_intervals); measured 17.2 ms per 2^20 x 64 launch vs 19.9 with 64-byte rows (3 waves per SIMD
     // instead of 2, but more draws past the row) and 35.0 with 256-byte rows (1 wave); R 72..112 the same
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100;
+    static constexpr int STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100, STAGE_RF = STAGE_R;
     static constexpr int RESTAGE_B = 8;   // row loads in flight per lane and restage pass (128-byte rows: 8 > 4 > 1)
     static constexpr int MIN_WAVES = 3;   // the LDS (stage rows + scratch) allows 3 blocks of 4 waves per CU
     static constexpr int EPW = 64;        // rollout envs per wave (lane_ctx)
-    static constexpr int REFILL_K = 2;   // stale blocks twisted per pass (see mt_refill_wave)
 
     uint32_t* s;       // lane scratch: word i at s[i * WAVE]: 0 = state word 13, 1 = 14, 2 = 30, 3 + q = 15 + q
     int infinite;

@@ -44,47 +44,11 @@ struct Col {
     }
 };
 
-// numpy init_by_array (mt19937_init_by_array) into a column; the state then awaits its first twist
-__device__ void init_by_array(const Col& mt, const uint32_t* key, int klen)
-{
-    uint32_t prev = 19650218u;
-    mt.set(0, prev);
-    for (int i = 1; i < MT_N; i++) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        mt.set(i, prev);
-    }
-    int i = 1, j = 0;
-    prev = mt.get(0);
-    for (int k = MT_N; k; k--) {
-        const uint32_t v = (mt.get(i) ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
-        mt.set(i, v);
-        prev = v;
-        i++;
-        j++;
-        if (i >= MT_N) { mt.set(0, mt.get(MT_N - 1)); prev = mt.get(0); i = 1; }
-        if (j >= klen) j = 0;
-    }
-    for (int k = MT_N - 1; k; k--) {
-        const uint32_t v = (mt.get(i) ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;
-        mt.set(i, v);
-        prev = v;
-        i++;
-        if (i >= MT_N) { mt.set(0, mt.get(MT_N - 1)); prev = mt.get(0); i = 1; }
-    }
-    mt.set(0, 0x80000000u);
-}
-
 // the env's RandomState as plain words: pos = words of the current block consumed (MT_N: twist before the next)
 struct WordRng {
     Col mt;
     uint32_t pos;
-    __device__ void twist() const   // numpy's reload, in place (mt[k] reads mt[k + 1], mt[k + 397] / the new mt[k - 227])
-    {
-        for (int k = 0; k < MT_N - MT_M; k++) mt.set(k, mt_mix(mt.get(k), mt.get(k + 1), mt.get(k + MT_M)));
-        for (int k = MT_N - MT_M; k < MT_N - 1; k++)
-            mt.set(k, mt_mix(mt.get(k), mt.get(k + 1), mt.get(k + MT_M - MT_N)));
-        mt.set(MT_N - 1, mt_mix(mt.get(MT_N - 1), mt.get(0), mt.get(MT_M - 1)));
-    }
+    __device__ void twist() const { mt_twist_inplace(mt); }   // numpy's reload, in place
     __device__ __forceinline__ uint32_t next()
     {
         if (pos >= (uint32_t)MT_N) {
@@ -298,7 +262,7 @@ __global__ __launch_bounds__(BLOCK) void k_seed(uint32_t* mt, uint32_t* ctl, uin
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= count) return;
     const int64_t env = first + i;
-    init_by_array(Col{mt + env, n}, keys + 2 * i, klen[i] == 2 ? 2 : 1);
+    mt_init_by_array(Col{mt + env, n}, keys + 2 * i, klen[i] == 2 ? 2 : 1);
     ctl[env] = (uint32_t)MT_N;   // numpy's state after seeding: the first draw twists
     Shoe g;
     g.s = Col{st + env, n};

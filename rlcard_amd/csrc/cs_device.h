@@ -1,19 +1,14 @@
 // cs_device.h -- device building blocks shared by every game kernel (gfx950 / CDNA4, wave64).
 //
 // Per-env RNG contract: numpy's legacy RandomState (MT19937) seeded by init_by_array with the key of
-// rlcard/utils/seeding.py:33-113, never re-seeded across resets (rlcard/envs/env.py:228-231). Layout in HBM:
-//   mt[env][2][624]  u32, env-major. The env's tempered stream is block0, block1, block0', ... where every block is
-//                    the MT19937 twist of the previous one. A lane reads its own words sequentially (every 128-B line
-//                    is reused 32 times out of L2), and a block refill is ONE contiguous 2.5 KB read + write done by
-//                    the whole wave cooperatively (mt_twist_wave), so the refill traffic is fully coalesced.
-//   ctl[env]         u32: bits 0..10 = stream position (0..1247), bit 16 = "the block not holding pos is stale".
-// A lane that steps past the end of its current block marks the block it left stale; at the end of every lockstep step
-// the wave refills all stale blocks (ballot + one cooperative twist per stale lane). A lane that would enter a stale
-// block inside a step (more than 624 draws in one step -- only possible through the rejection loop's tail) twists it
-// in-lane (mt_twist_serial): slow, never on the fast path, same numbers.
+// rlcard/utils/seeding.py:33-113, never re-seeded across resets (rlcard/envs/env.py:228-231). This header holds the
+// MT19937 arithmetic every layout shares (init_by_array, the in-place twist, mix, temper). How an env's stream is kept
+// in HBM is the game's: the lane-per-env games' ring of tempered low bytes (cs_ring.h), DouDizhu's two word blocks
+// (cs_doudizhu.hip, WaveMt), the Blackjack shoe's word column (cs_blackjack_shoe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "cs_prof.h"
 
@@ -36,8 +31,6 @@ __device__ __forceinline__ void out_store(T* p, T v)
 
 constexpr int MT_N = 624;
 constexpr int MT_M = 397;
-constexpr int MT_WORDS = 2 * MT_N;
-constexpr uint32_t CTL_STALE = 1u << 16;
 constexpr int WAVE = 64;
 
 // runtime game configuration (cs_config): blackjack reads players / decks, no-limit hold'em stacks / dealer
@@ -47,6 +40,23 @@ struct GameParams {
     int32_t chips_for_each;   // no-limit: stack per player
     int32_t dealer_id;        // no-limit: -1 = drawn by the first reset (rlcard's None), else fixed
     int32_t rng_mode;         // CS_RNG_MT19937 (reference-compatible) or CS_RNG_PHILOX (cs_ring.h)
+};
+
+// What a skeleton game type (cs_skeleton.h) inherits unless it states otherwise
+struct GameDefaults {
+    // k_rollout: the lane id made opaque at every step. Round 5, same box: Limit 8.18 -> 8.07 ms and No-limit 9.33 ->
+    // 9.10 without it, Blackjack 20.62 -> 20.89 and Leduc even
+    static constexpr bool LANE_OPAQUE = true;
+    // the 8-B reward row's value made opaque before its nontemporal store: without it the optimizer may split the store
+    // back into two float stores and drop the nontemporal hint on the way (No-limit's rollout); with it where the hint
+    // survives anyway (Leduc, Limit) the step schedules worse (Leduc 4.23 -> 4.48 ms, round 5)
+    static constexpr bool REWARD_OPAQUE = false;
+    // Env.get_payoffs at the step that ends the game takes the lane's RNG: games whose judge may draw from the env's
+    // stream (N-player hold'em's odd split remainders, limitholdem/judger.py:80-83)
+    static constexpr bool PAYOFF_DRAWS = false;
+    static constexpr int SPARSE_K = 0;     // > 0: obs rows are one-hot with SPARSE_K known positions (observe_pos)
+    static constexpr int MAX_POLICY = 0;   // > 0: the largest CS_POLICY_* id of the game's rule_action
+    static constexpr int DQ = 0;           // > 0: deals drawn ahead into a queue of this depth (cs_dq.h)
 };
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
@@ -77,49 +87,60 @@ __device__ __forceinline__ uint32_t mt_mix(uint32_t cur, uint32_t nxt, uint32_t 
     return far ^ (y >> 1) ^ ((0u - (nxt & 1u)) & 0x9908b0dfu);
 }
 
-// dst = twist(src), one lane, in-order (rare slow path and the seeding kernel)
-__device__ inline void mt_twist_serial(const uint32_t* src, uint32_t* dst)
+// The 624 state words behind `mt`: a plain pointer, or an accessor with get(k) / set(k, v) (the shoe's Col)
+template <class M>
+__device__ __forceinline__ uint32_t mt_get(M mt, int k)
 {
-    for (int k = 0; k < MT_N - MT_M; k++) dst[k] = mt_mix(src[k], src[k + 1], src[k + MT_M]);
-    for (int k = MT_N - MT_M; k < MT_N - 1; k++) dst[k] = mt_mix(src[k], src[k + 1], dst[k - (MT_N - MT_M)]);
-    dst[MT_N - 1] = mt_mix(src[MT_N - 1], dst[0], dst[MT_M - 1]);
+    if constexpr (std::is_pointer<M>::value) return mt[k];
+    else return mt.get(k);
+}
+template <class M>
+__device__ __forceinline__ void mt_set(M mt, int k, uint32_t v)
+{
+    if constexpr (std::is_pointer<M>::value) mt[k] = v;
+    else mt.set(k, v);
 }
 
-// dst = twist(src) computed by all 64 lanes of the wave (every lane must call it with the same src/dst).
-// The recurrence new[k] = f(old[k], old[k+1] | new[0], old[k+397] | new[k-227]) splits into three dependency
-// phases of <= 227 words; phase p's dependency for word k sits in the SAME lane and chunk of phase p-1, so
-// everything stays in registers; only new[0] crosses lanes (readlane).
-__device__ __forceinline__ void mt_twist_wave(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int lane)
+// numpy init_by_array (mt19937_init_by_array); the state then awaits its first twist
+template <class M>
+__device__ inline void mt_init_by_array(M mt, const uint32_t* key, int klen)
 {
-    constexpr int H = MT_N - MT_M;  // 227
-    uint32_t n1[4], n2[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = 64 * c + lane;
-        if (k < H) {
-            n1[c] = mt_mix(src[k], src[k + 1], src[k + MT_M]);
-            dst[k] = n1[c];
-        } else {
-            n1[c] = 0;
-        }
+    uint32_t prev = 19650218u;
+    mt_set(mt, 0, prev);
+    for (int i = 1; i < MT_N; i++) {
+        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
+        mt_set(mt, i, prev);
     }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = H + 64 * c + lane;
-        if (k < 2 * H) {
-            n2[c] = mt_mix(src[k], src[k + 1], n1[c]);
-            dst[k] = n2[c];
-        } else {
-            n2[c] = 0;
-        }
+    int i = 1, j = 0;
+    prev = mt_get(mt, 0);
+    for (int k = MT_N; k; k--) {
+        const uint32_t v = (mt_get(mt, i) ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
+        mt_set(mt, i, v);
+        prev = v;
+        i++;
+        j++;
+        if (i >= MT_N) { mt_set(mt, 0, mt_get(mt, MT_N - 1)); prev = mt_get(mt, 0); i = 1; }
+        if (j >= klen) j = 0;
     }
-    const uint32_t new0 = __builtin_amdgcn_readlane(n1[0], 0);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int k = 2 * H + 64 * c + lane;
-        if (k < MT_N - 1) dst[k] = mt_mix(src[k], src[k + 1], n2[c]);
-        else if (k == MT_N - 1) dst[k] = mt_mix(src[k], new0, n2[c]);
+    for (int k = MT_N - 1; k; k--) {
+        const uint32_t v = (mt_get(mt, i) ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;
+        mt_set(mt, i, v);
+        prev = v;
+        i++;
+        if (i >= MT_N) { mt_set(mt, 0, mt_get(mt, MT_N - 1)); prev = mt_get(mt, 0); i = 1; }
     }
+    mt_set(mt, 0, 0x80000000u);
+}
+
+// numpy's twist (genrand_int32's reload), in place: mt[k] only reads mt[k+1], mt[k+397] (not yet rewritten) and the
+// already-new mt[k-227]
+template <class M>
+__device__ inline void mt_twist_inplace(M mt)
+{
+    for (int k = 0; k < MT_N - MT_M; k++) mt_set(mt, k, mt_mix(mt_get(mt, k), mt_get(mt, k + 1), mt_get(mt, k + MT_M)));
+    for (int k = MT_N - MT_M; k < MT_N - 1; k++)
+        mt_set(mt, k, mt_mix(mt_get(mt, k), mt_get(mt, k + 1), mt_get(mt, k + MT_M - MT_N)));
+    mt_set(mt, MT_N - 1, mt_mix(mt_get(mt, MT_N - 1), mt_get(mt, 0), mt_get(mt, MT_M - 1)));
 }
 
 // Global-address-space view of a pointer into HBM: pointers rebuilt from integers (readlane) are generic, and generic
@@ -127,7 +148,6 @@ __device__ __forceinline__ void mt_twist_wave(const uint32_t* __restrict__ src, 
 // -- draining the wave's outstanding trajectory stores each time (measured in the k_rollout ISA)
 typedef __attribute__((address_space(1))) uint32_t gu32;
 typedef __attribute__((address_space(1))) uint8_t gu8;
-__device__ __forceinline__ gu32* to_global(uint32_t* p) { return (gu32*)p; }
 
 // 64-bit pointer held by lane j (readlane returns int: go through uint32_t so bit 31 of the low half is not
 // sign-extended into the high half)
@@ -139,211 +159,18 @@ __device__ __forceinline__ gu32* lane_ptr(uint32_t* p, int j)
     return (gu32*)(uintptr_t)(lo | (hi << 32));
 }
 
-// One lane's view of its env's stream. MODE selects how draws are served:
+// How a lane's view of its env's byte ring (cs_ring.h RingLane<MODE>) serves draws:
 //   STAGE_NONE  one global load per draw (single-step kernels: staging would cost more than it saves);
 //   STAGE_LDS   W staged bytes in a per-lane LDS row (the rollout kernels).
 // Why staging: lanes sit at different stream positions, so one load per draw is a 64-line gather per wave
 // instruction, and a reset's rejection loops issue one such gather per trip of the slowest lane (rocprofv3 on
 // k_rollout<Leduc>: TA busy 68% of the kernel, ~300 L1 accesses per wave-step, waves waiting 80% of their cycles).
-// Every draw of this engine is random_interval(max <= 53), which looks only at the low 8 bits of the tempered word,
-// so at step boundaries (after the refill: both blocks valid) lanes running low restage their next words, temper
-// them and keep the low bytes; draws then read LDS, global only as a fallback when a lane outruns its stage.
+// Every draw of the lane-per-env games is random_interval(max <= 53), which looks only at the low 8 bits of the
+// tempered word, so at step boundaries (after the refill) lanes running low restage their next ring bytes; draws then
+// read LDS, global only as a fallback when a lane outruns its stage.
 // Measured on MI355X (tools/ab_rollout.py): staging beat one load per draw by 13-30 %; register variants (a per-draw
 // 8-word window, 8/16-word bursts inside the reset, 16 staged bytes in 4 VGPRs) all lost to it.
 enum { STAGE_NONE = 0, STAGE_LDS = 2 };
-
-template <int MODE = STAGE_NONE>
-struct MtLaneT {
-    static constexpr int kMode = MODE;
-    uint32_t* base;  // mt + env * MT_WORDS
-    uint32_t pos;
-    uint32_t stale;
-    uint32_t sp, sn;            // stream position of staged byte 0; staged bytes
-    const uint8_t* stg;         // STAGE_LDS: this lane's row
-
-    __device__ __forceinline__ void init(uint32_t* p_base, uint32_t p, uint32_t s)
-    {
-        base = p_base;
-        pos = p;
-        stale = s;
-        sp = 0;
-        sn = 0;
-        stg = nullptr;
-    }
-
-    __device__ __forceinline__ void advance()
-    {
-        pos++;
-        if (pos == MT_N || pos == MT_WORDS) {
-            const uint32_t from = pos - MT_N;           // start of the block just finished
-            if (pos == MT_WORDS) pos = 0;
-            if (stale) mt_twist_serial(base + from, base + pos);   // entering a block nobody refilled yet
-            stale = 1;
-        }
-    }
-
-    __device__ __forceinline__ uint32_t next()
-    {
-        const uint32_t y = base[pos];
-        advance();
-        return mt_temper(y);
-    }
-
-    __device__ __forceinline__ uint32_t staged_offset() const { return pos >= sp ? pos - sp : pos + MT_WORDS - sp; }
-
-    // low 8 bits of the next tempered word
-    __device__ __forceinline__ uint32_t next8()
-    {
-        uint32_t v;
-        if constexpr (MODE == STAGE_NONE) {
-            v = mt_temper(base[pos]) & 255u;
-        } else {
-            const uint32_t k = staged_offset();
-            if (k < sn) {
-                v = stg[k];
-            } else {
-                v = mt_temper(base[pos]) & 255u;
-            }
-        }
-        advance();
-        return v;
-    }
-
-    // numpy random_interval(max): smallest all-ones mask >= max, reject while (u32 & mask) > max
-    __device__ __forceinline__ uint32_t interval(uint32_t max)
-    {
-        if (max == 0) return 0;
-        uint32_t mask = max;
-        mask |= mask >> 1;
-        mask |= mask >> 2;
-        mask |= mask >> 4;
-        mask |= mask >> 8;
-        mask |= mask >> 16;
-        uint32_t v;
-        if (max <= 255u) {
-            do {
-                v = next8() & mask;
-            } while (v > max);
-        } else {
-            do {
-                v = next() & mask;
-            } while (v > max);
-        }
-        return v;
-    }
-
-    // pos += n (n < 624 staged words), with advance()'s block bookkeeping
-    __device__ __forceinline__ void advance_by(uint32_t n)
-    {
-        uint32_t np = pos + n;
-        const bool crossed = pos < (uint32_t)MT_N ? np >= (uint32_t)MT_N : np >= (uint32_t)MT_WORDS;
-        if (np >= (uint32_t)MT_WORDS) np -= MT_WORDS;
-        if (crossed) {
-            if (stale) mt_twist_serial(base + (np < (uint32_t)MT_N ? MT_N : 0), base + (np < (uint32_t)MT_N ? 0 : MT_N));
-            stale = 1;
-        }
-        pos = np;
-    }
-
-    // random_interval(i) for i = hi, hi - 1, ..., 1 with every result discarded (shuffle positions nobody is dealt
-    // from): acceptance only decides how many words are consumed, so the staged bytes are scanned branch-free, four
-    // per LDS read. A lane that runs out of staged bytes finishes through interval() (global loads).
-    __device__ __forceinline__ void skip_intervals(uint32_t hi)
-    {
-        uint32_t i = hi;
-        if constexpr (MODE == STAGE_LDS) {
-            const uint32_t k0 = staged_offset();
-            uint32_t k = k0;
-            while (i != 0 && k < sn) {
-                const uint32_t sh = k & 3u;
-                const uint32_t w = *(const uint32_t*)(stg + (k - sh)) >> (8 * sh);
-#pragma unroll
-                for (uint32_t t = 0; t < 4; t++) {
-                    if (t < 4 - sh && i != 0 && k < sn) {
-                        const uint32_t u = (w >> (8 * t)) & (0xFFFFFFFFu >> __builtin_clz(i));
-                        i -= u <= i ? 1u : 0u;
-                        k++;
-                    }
-                }
-            }
-            advance_by(k - k0);
-        }
-        for (; i >= 1; i--) (void)interval(i);
-    }
-};
-using MtLane = MtLaneT<STAGE_NONE>;
-
-// dst[s] = twist(src[s]) for K streams at once, phases interleaved so the K twists' loads overlap (see mt_twist_wave)
-template <int K>
-__device__ __forceinline__ void mt_twist_wave_k(const gu32* const (&src)[K], gu32* const (&dst)[K], int lane)
-{
-    constexpr int H = MT_N - MT_M;  // 227
-    uint32_t n1[K][4], n2[K][4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = 64 * c + lane;
-#pragma unroll
-        for (int s = 0; s < K; s++) n1[s][c] = k < H ? mt_mix(src[s][k], src[s][k + 1], src[s][k + MT_M]) : 0u;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = 64 * c + lane;
-#pragma unroll
-        for (int s = 0; s < K; s++)
-            if (k < H) dst[s][k] = n1[s][c];
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = H + 64 * c + lane;
-#pragma unroll
-        for (int s = 0; s < K; s++) n2[s][c] = k < 2 * H ? mt_mix(src[s][k], src[s][k + 1], n1[s][c]) : 0u;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int k = H + 64 * c + lane;
-#pragma unroll
-        for (int s = 0; s < K; s++)
-            if (k < 2 * H) dst[s][k] = n2[s][c];
-    }
-#pragma unroll
-    for (int s = 0; s < K; s++) {
-        const uint32_t new0 = __builtin_amdgcn_readlane(n1[s][0], 0);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const int k = 2 * H + 64 * c + lane;
-            if (k < MT_N - 1) dst[s][k] = mt_mix(src[s][k], src[s][k + 1], n2[s][c]);
-            else if (k == MT_N - 1) dst[s][k] = mt_mix(src[s][k], new0, n2[s][c]);
-        }
-    }
-}
-
-// End-of-step convergence point: the wave refills every stale block of its lanes, two lanes' twists at a time
-// (their loads overlap; an odd last lane is paired with itself: identical writes, harmless). All 64 lanes must call.
-template <int K = 2, class M>
-__device__ __forceinline__ void mt_refill_wave(M& m, int lane)
-{
-    uint64_t need = __ballot(m.stale != 0);
-    while (need) {
-        const gu32* src[K];
-        gu32* dst[K];
-        int j0 = -1;
-#pragma unroll
-        for (int s = 0; s < K; s++) {
-            const int j = need ? __builtin_ctzll(need) : j0;
-            need &= need - 1;
-            if (s == 0) j0 = j;
-            gu32* b = lane_ptr(m.base, j);
-            const uint32_t c = __builtin_amdgcn_readlane(m.pos, j) < MT_N ? 0 : MT_N;
-            src[s] = b + c;
-            dst[s] = b + (MT_N - c);
-        }
-        mt_twist_wave_k<K>(src, dst, lane);
-    }
-    m.stale = 0;
-    // the refilled words are read later by their owner lane of this same wave: order the stores before those loads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // STAGE_LDS rows: W bytes per lane (W multiple of 64), row stride W + PAD (per game): LDS bounds occupancy, so the
 // pad is as small as the measurements allow (steady-state A/B on MI355X: Leduc W 64 + 4 fits 6 blocks per CU and is
@@ -363,61 +190,6 @@ __device__ __forceinline__ void wave_sync_lds()
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// STAGE_LDS restage, after mt_refill_wave: every lane with fewer than R staged draws left gets its next W words,
-// loaded COALESCED by the whole wave (all 64 lanes read one lane's consecutive words), tempered and packed to bytes
-// (lanes 4q gather lanes 4q+1..3 with DPP row shifts: VALU, no LDS traffic). area = the wave's staging area (lane j's
-// row at area + j * STRIDE). All 64 lanes must call.
-template <int W, int PAD, int R, int B>
-__device__ __forceinline__ void mt_restage_wave(MtLaneT<STAGE_LDS>& m, uint8_t* area, int lane, bool valid)
-{
-    constexpr int STRIDE = Stage<W, PAD>::STRIDE, C = W / WAVE;
-    m.stg = area + lane * STRIDE;
-    const uint32_t k = m.staged_offset();
-    uint64_t todo = __ballot(valid && (k >= m.sn || m.sn - k < (uint32_t)R));
-    while (todo) {
-        // B needy lanes per pass, all their loads issued before the first is used (a pass with fewer than B left
-        // repeats its first lane: same words, same bytes, harmless)
-        int js[B];
-        js[0] = __builtin_ctzll(todo);
-        todo &= todo - 1;
-#pragma unroll
-        for (int b = 1; b < B; b++) {
-            js[b] = todo ? __builtin_ctzll(todo) : js[0];
-            todo &= todo - 1;
-        }
-        uint32_t ps[B], v[B][C];
-#pragma unroll
-        for (int b = 0; b < B; b++) {
-            const gu32* jb = lane_ptr(m.base, js[b]);
-            ps[b] = __builtin_amdgcn_readlane(m.pos, js[b]);
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                uint32_t idx = ps[b] + (uint32_t)(c * WAVE + lane);
-                if (idx >= (uint32_t)MT_WORDS) idx -= MT_WORDS;
-                v[b][c] = jb[idx];
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < B; b++) {
-#pragma unroll
-            for (int c = 0; c < C; c++) {
-                const int t = (int)(mt_temper(v[b][c]) & 255u);
-                const uint32_t t1 = (uint32_t)__builtin_amdgcn_update_dpp(0, t, 0x101, 0xF, 0xF, true);  // row_shl:1
-                const uint32_t t2 = (uint32_t)__builtin_amdgcn_update_dpp(0, t, 0x102, 0xF, 0xF, true);  // row_shl:2
-                const uint32_t t3 = (uint32_t)__builtin_amdgcn_update_dpp(0, t, 0x103, 0xF, 0xF, true);  // row_shl:3
-                if ((lane & 3) == 0)
-                    *(uint32_t*)(area + js[b] * STRIDE + c * WAVE + lane) =
-                        (uint32_t)t | (t1 << 8) | (t2 << 16) | (t3 << 24);
-            }
-            if (lane == js[b]) {
-                m.sp = ps[b];
-                m.sn = W;
-            }
-        }
-    }
-    wave_sync_lds();
 }
 
 // Persist / restore a wave's staging rows (W bytes per env, HBM row-major [env][W]) with coalesced 16-B / 8-B copies, so a
@@ -495,7 +267,7 @@ struct PolicyRng {
     }
 };
 
-// uniform pick among the set bits of a <= 64-action legal mask (k = floor(r * count / 2^32), k-th set bit)
+// uniform pick among the set bits of a <= 32-action legal mask (k = floor(r * count / 2^32), k-th set bit)
 __device__ __forceinline__ int pick_legal32(uint32_t legal, uint32_t r)
 {
     const int count = __popc(legal);
@@ -515,14 +287,6 @@ __device__ __forceinline__ int pick_legal_small(uint32_t legal, uint32_t r)
 #pragma unroll
     for (uint32_t i = 0; i + 1 < (uint32_t)A; i++) legal = i < k ? legal & (legal - 1u) : legal;
     return count == 0 ? -1 : __builtin_ctz(legal);
-}
-__device__ __forceinline__ int pick_legal(uint64_t legal, uint32_t r)
-{
-    const int count = __popcll(legal);
-    if (count == 0) return -1;
-    int k = (int)(((uint64_t)r * (uint64_t)count) >> 32);
-    while (k--) legal &= legal - 1;
-    return __builtin_ctzll(legal);
 }
 
 // ---- coalesced output of per-lane byte rows ------------------------------------------------------------------------

@@ -91,24 +91,6 @@ CS_DDZ_HD uint32_t simple_gid(uint32_t id, uint32_t bomb_lo, uint32_t bomb_g)
 enum { W_HAND = 0, W_PLAYED = 6, W_HIST = 12, W_NTRACE = 17, W_GREATER = 18, W_CUR = 19, W_DECK = 20 };
 constexpr int DECK_BYTES = 4 * (WORDS - W_DECK);   // 64: bytes 54..63 zero
 
-// The state k_seed writes (lane per env, like every other game): a finished game (winner 0), so the next
-// reset/step deals.
-struct SeedView {
-    static constexpr int SCRATCH_WORDS = 0;
-    static constexpr bool RING = false;   // doudizhu keeps the two-block word layout (cs_doudizhu.hip)
-    template <class Prm>
-    __host__ __device__ void bind(uint32_t*, const Prm&) {}
-    __host__ __device__ void blank() {}
-    __host__ __device__ void store(uint32_t* st, int64_t, int64_t env) const
-    {
-        uint32_t* w = st + env * WORDS;
-        for (int k = 0; k < WORDS; k++) w[k] = 0;
-        for (int k = W_HIST; k < W_HIST + 5; k++) w[k] = 0xFFFFFFFFu;
-        w[W_GREATER] = NONE;
-        w[W_CUR] = 0u | (0u << 8);
-    }
-};
-
 #ifdef __HIPCC__
 // _cards2array (envs/doudizhu.py:150-166) of packed counts: bit 4r + k = (count_r > k) for r < 13, bit 52 / 53 = jokers
 __device__ __forceinline__ uint64_t cards_bits(uint64_t c)

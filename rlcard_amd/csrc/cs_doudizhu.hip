@@ -245,6 +245,134 @@ __device__ __forceinline__ uint32_t decode_action(int32_t a, const Env& e, const
 }
 
 // ---- MT19937 stream of this env, read by the whole wave --------------------------------------------------------
+// Layout in HBM (DouDizhu only; the lane-per-env games keep a byte ring, cs_ring.h):
+//   mt[env][2][624]  u32, env-major. The env's tempered stream is block0, block1, block0', ... where every block is
+//                    the MT19937 twist of the previous one. A block refill is ONE contiguous 2.5 KB read + write done
+//                    by the whole wave cooperatively (mt_twist_wave), so the refill traffic is fully coalesced.
+//   ctl[env]         u32: bits 0..10 = stream position (0..1247), bit 16 = "the block not holding pos is stale".
+// Every draw reads a word. A wave that consumes past the end of its current block marks the block it left stale and
+// twists it just before a window would reach it (WaveMt::window). Seeding (k_seed, a lane per env) fills both blocks:
+// the first in-lane (mt_twist_serial), the second by the wave for each of its lanes in turn (mt_refill_wave).
+constexpr int MT_WORDS = 2 * MT_N;
+
+// dst = twist(src), one lane, in-order (the seeding kernel)
+__device__ inline void mt_twist_serial(const uint32_t* src, uint32_t* dst)
+{
+    for (int k = 0; k < MT_N - MT_M; k++) dst[k] = mt_mix(src[k], src[k + 1], src[k + MT_M]);
+    for (int k = MT_N - MT_M; k < MT_N - 1; k++) dst[k] = mt_mix(src[k], src[k + 1], dst[k - (MT_N - MT_M)]);
+    dst[MT_N - 1] = mt_mix(src[MT_N - 1], dst[0], dst[MT_M - 1]);
+}
+
+// dst = twist(src) computed by all 64 lanes of the wave (every lane must call it with the same src/dst).
+// The recurrence new[k] = f(old[k], old[k+1] | new[0], old[k+397] | new[k-227]) splits into three dependency
+// phases of <= 227 words; phase p's dependency for word k sits in the SAME lane and chunk of phase p-1, so
+// everything stays in registers; only new[0] crosses lanes (readlane).
+__device__ __forceinline__ void mt_twist_wave(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int lane)
+{
+    constexpr int H = MT_N - MT_M;  // 227
+    uint32_t n1[4], n2[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = 64 * c + lane;
+        if (k < H) {
+            n1[c] = mt_mix(src[k], src[k + 1], src[k + MT_M]);
+            dst[k] = n1[c];
+        } else {
+            n1[c] = 0;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = H + 64 * c + lane;
+        if (k < 2 * H) {
+            n2[c] = mt_mix(src[k], src[k + 1], n1[c]);
+            dst[k] = n2[c];
+        } else {
+            n2[c] = 0;
+        }
+    }
+    const uint32_t new0 = __builtin_amdgcn_readlane(n1[0], 0);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int k = 2 * H + 64 * c + lane;
+        if (k < MT_N - 1) dst[k] = mt_mix(src[k], src[k + 1], n2[c]);
+        else if (k == MT_N - 1) dst[k] = mt_mix(src[k], new0, n2[c]);
+    }
+}
+
+// dst[s] = twist(src[s]) for K streams at once, phases interleaved so the K twists' loads overlap (see mt_twist_wave)
+template <int K>
+__device__ __forceinline__ void mt_twist_wave_k(const gu32* const (&src)[K], gu32* const (&dst)[K], int lane)
+{
+    constexpr int H = MT_N - MT_M;  // 227
+    uint32_t n1[K][4], n2[K][4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = 64 * c + lane;
+#pragma unroll
+        for (int s = 0; s < K; s++) n1[s][c] = k < H ? mt_mix(src[s][k], src[s][k + 1], src[s][k + MT_M]) : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = 64 * c + lane;
+#pragma unroll
+        for (int s = 0; s < K; s++)
+            if (k < H) dst[s][k] = n1[s][c];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = H + 64 * c + lane;
+#pragma unroll
+        for (int s = 0; s < K; s++) n2[s][c] = k < 2 * H ? mt_mix(src[s][k], src[s][k + 1], n1[s][c]) : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const int k = H + 64 * c + lane;
+#pragma unroll
+        for (int s = 0; s < K; s++)
+            if (k < 2 * H) dst[s][k] = n2[s][c];
+    }
+#pragma unroll
+    for (int s = 0; s < K; s++) {
+        const uint32_t new0 = __builtin_amdgcn_readlane(n1[s][0], 0);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int k = 2 * H + 64 * c + lane;
+            if (k < MT_N - 1) dst[s][k] = mt_mix(src[s][k], src[s][k + 1], n2[s][c]);
+            else if (k == MT_N - 1) dst[s][k] = mt_mix(src[s][k], new0, n2[s][c]);
+        }
+    }
+}
+
+// Convergence point of lanes that each hold an env (the seeding kernel): the wave refills every stale block of its
+// lanes, two lanes' twists at a time (their loads overlap; an odd last lane is paired with itself: identical writes,
+// harmless). All 64 lanes must call.
+template <int K = 2, class M>
+__device__ __forceinline__ void mt_refill_wave(M& m, int lane)
+{
+    uint64_t need = __ballot(m.stale != 0);
+    while (need) {
+        const gu32* src[K];
+        gu32* dst[K];
+        int j0 = -1;
+#pragma unroll
+        for (int s = 0; s < K; s++) {
+            const int j = need ? __builtin_ctzll(need) : j0;
+            need &= need - 1;
+            if (s == 0) j0 = j;
+            gu32* b = lane_ptr(m.base, j);
+            const uint32_t c = __builtin_amdgcn_readlane(m.pos, j) < MT_N ? 0 : MT_N;
+            src[s] = b + c;
+            dst[s] = b + (MT_N - c);
+        }
+        mt_twist_wave_k<K>(src, dst, lane);
+    }
+    m.stale = 0;
+    // the refilled words are read later by their owner lane of this same wave: order the stores before those loads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // Philox mode (cs_config.rng_mode = CS_RNG_PHILOX, ctl bit 18; not the reference's deals): draw k is byte k % 16 of
 // Philox4x32-10(key = the env's init_by_array key, counter = (k / 624, (k % 624) / 16)) -- the lane-per-env games'
 // Philox byte stream (cs_ring.h), so every rule and the oracle's restatement (oracle/or_rng.c) are shared. The draws
@@ -670,6 +798,46 @@ __device__ __forceinline__ void payoffs(uint32_t winner, float* r)   // judger.p
     r[2] = r[1];
 }
 __device__ __forceinline__ void payoffs(const Env& e, float* r) { payoffs(e.winner, r); }
+
+// Seeding, a lane per env (env first + i takes key i), unlike every other kernel here: the env's stream, then a
+// finished game (winner 0), so the next reset / step deals. flags bit 0: the second block is twisted in-lane too.
+__global__ __launch_bounds__(BLOCK) void k_seed(uint32_t* mt, uint32_t* ctl, uint32_t* st, const uint32_t* keys,
+                                                 const int32_t* klen, int64_t first, int64_t count, int flags,
+                                                 bool phx)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const bool valid = i < count;
+    const int64_t env = first + i;
+    WaveMt<false> m{mt, 0, 0, 0, 0};   // nothing stale: a lane without an env asks for no refill
+    if (valid) {
+        uint32_t* base = mt + env * MT_WORDS;
+        const int kl = klen[i] == 2 ? 2 : 1;                    // validated on the host; never trust it here
+        if (phx) {   // the key in words 0..1, draw count 0 in word 2 (WaveMt)
+            base[0] = keys[2 * i];
+            base[1] = kl == 2 ? keys[2 * i + 1] : 0u;
+            base[2] = 0u;
+        } else {
+            mt_init_by_array(base + MT_N, keys + 2 * i, kl);    // S0 in block 1 (scratch)
+            mt_twist_serial(base + MT_N, base);                 // block 0 = twist(S0): numpy's first draws
+            m.base = base;
+            m.stale = 1;                                        // block 1 = twist(block 0), refilled below
+        }
+        uint32_t* w = st + env * WORDS;
+        for (int k = 0; k < WORDS; k++) w[k] = 0;
+        for (int k = W_HIST; k < W_HIST + 5; k++) w[k] = 0xFFFFFFFFu;
+        w[W_GREATER] = NONE;
+        w[W_CUR] = 0u | (0u << 8);
+    }
+    if (!phx) {   // uniform
+        if (flags & 1) {
+            if (valid) mt_twist_serial(m.base, m.base + MT_N);
+        } else {
+            mt_refill_wave(m, lane);
+        }
+    }
+    if (valid) ctl[env] = phx ? CTL_PHX : 0u;
+}
 
 template <bool PHX>
 __global__ __launch_bounds__(BLOCK) void k_reset(uint32_t* mt, uint32_t* ctl, uint32_t* st, int64_t n,
@@ -1554,6 +1722,13 @@ hipError_t launch_debug_legal(const Buffers& b, const uint8_t* counts, const int
     return hipGetLastError();
 }
 
+hipError_t launch_seed(const Buffers& b, const uint32_t* keys, const int32_t* klen, int64_t first, int64_t count,
+                       hipStream_t s)
+{
+    hipLaunchKernelGGL(k_seed, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state,
+                       keys, klen, first, count, b.kernel_flags, b.rng_mode == CS_RNG_PHILOX);
+    return hipGetLastError();
+}
 hipError_t launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s)
 {
     if (b.rng_mode == CS_RNG_PHILOX)
@@ -1583,7 +1758,7 @@ hipError_t launch_rollout(const Buffers& b, int32_t T, uint64_t seed, uint64_t t
                           const cs_traj_out& o, hipStream_t s)
 {
     const dim3 g((unsigned)((b.n + 2 * PWPB - 1) / (2 * PWPB)));
-    const PairArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, *(const Tab*)b.table, T, b.serial_refill};
+    const PairArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, *(const Tab*)b.table, T, b.kernel_flags};
     if (b.rng_mode == CS_RNG_PHILOX) hipLaunchKernelGGL(k_rollout2<true>, g, dim3(PBLOCK), 0, s, a);
     else hipLaunchKernelGGL(k_rollout2<false>, g, dim3(PBLOCK), 0, s, a);
     return hipGetLastError();

@@ -2,18 +2,15 @@
 // cs_limit.h, cs_nolimit.h): deals drawn ahead, in stream order, popped by the game resets. Shared by the rollout
 // skeleton (cs_skeleton.h) and the CFR kernel (cs_cfr.hip), which resets through the same queue.
 #pragma once
-#include <type_traits>
 #include "cs_device.h"
+#include "cs_ring.h"   // RING: a deal's draw count is a difference of ring positions
 
 namespace cs {
 
 // ---- the deal queue: q = the env's queue words, `stride` apart (state in HBM: n; LDS copy: 1) ------
-template <class G, class = void>
-struct DqOf {
-    static constexpr int value = 0, words = 0, cb = 0, xb = 0;
-};
+// depth G::DQ (GameDefaults: 0, no queue) and the words it takes after the game's own
 template <class G>
-struct DqOf<G, std::void_t<decltype(G::DQ)>> {
+struct DqOf {
     static constexpr int value = G::DQ, words = G::DQ > 0 ? 1 + 2 * G::DQ : 0;
     // header fields (cs_limit.h): count bits, then head bits (cb - 1), from bit xb the dealer bits and draws[8:7]
     static constexpr int cb = G::DQ == 8 ? 4 : G::DQ == 4 ? 3 : 2, xb = 2 * cb - 1;

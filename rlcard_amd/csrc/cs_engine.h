@@ -25,7 +25,7 @@ struct StepRecord {
 struct Buffers {
     int32_t game;
     int64_t n;
-    uint32_t* mt;     // [n][1248]
+    uint32_t* mt;     // the envs' RNG words: [n][GameOps::mt_words], or [mt_words][n] where GameOps::mt_columns
     uint32_t* ctl;    // [n]
     uint32_t* state;  // [state_words][n] (lane-per-env games) or [n][state_words] (doudizhu, wave per env)
     uint32_t* sctl;   // [n] rollout MT staging: staged stream position | staged count << 16
@@ -33,7 +33,7 @@ struct Buffers {
     const void* table;  // game-specific read-only table (doudizhu action table), or null
     int32_t num_players, num_decks;
     int32_t chips_for_each, dealer_id;   // no-limit hold'em (cs_config; dealer_id -1 = drawn)
-    int32_t serial_refill;  // testing hook
+    int32_t kernel_flags;   // cs_debug_set_kernel_flags bits 0..2 (bit 0 alone: cs_debug_set_serial_refill)
     int32_t rng_mode;       // cs_config.rng_mode
     StepRecord rec;         // seq == nullptr: off
     int32_t obs_dim, num_actions, action_bytes;   // cs_game_info of the handle
@@ -133,7 +133,9 @@ hipError_t launch_rng_copy(const Buffers& b, int64_t env, int32_t mtw, int32_t c
                            uint32_t* buf, int32_t load, hipStream_t s);   // cs_traj.hip
 hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, hipStream_t s);   // cs_kernels.hip
 
-namespace ddz {   // cs_doudizhu.hip (seeding goes through the shared k_seed)
+namespace ddz {   // cs_doudizhu.hip
+hipError_t launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
+                       int64_t count, hipStream_t s);
 hipError_t launch_reset(const Buffers& b, const cs_step_out& o, hipStream_t s);
 hipError_t launch_step(const Buffers& b, const int32_t* actions, const cs_step_out& o, hipStream_t s);
 hipError_t launch_observe(const Buffers& b, int32_t player, const cs_step_out& o, hipStream_t s);

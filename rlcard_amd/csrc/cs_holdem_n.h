@@ -168,13 +168,13 @@ __device__ __forceinline__ int next_seat(int i) { return i + 1 == P ? 0 : i + 1;
 // player word: hand:3 in:5 (3) raised:5 (8) folded:1 (13)
 // shared word S: pub:3 rc:2 (3) ptr:3 (5) have_raised:2 (8) not_raise_num:4 (10) over:1 (31)
 template <int NP>
-struct LeducN {
+struct LeducN : GameDefaults {
     static_assert(NP >= 3 && NP <= 5, "leduc: 3..5 players");
     static constexpr int OBS = 36, A = 4, P = NP, LB = 1, WORDS = NP + 1, ACTION_BYTES = 1, NB = 2;
-    static constexpr bool RING = true, RAW_OBS = false, PAYOFF_DRAWS = false;
+    static constexpr bool RAW_OBS = false, PAYOFF_DRAWS = false;
     static constexpr int SCRATCH_WORDS = 0;
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 64, STAGE_PAD = 4, STAGE_R = 16, STAGE_RF = 24, RESTAGE_B = 4;
-    static constexpr int MIN_WAVES = 4, EPW = 64, REFILL_K = 1;
+    static constexpr int STAGE_W = 64, STAGE_PAD = 4, STAGE_R = 16, STAGE_RF = 24, RESTAGE_B = 4;
+    static constexpr int MIN_WAVES = 4, EPW = 64;
     enum { CALL = 0, RAISE = 1, FOLD = 2, CHECK = 3 };
     __device__ __forceinline__ void bind(uint32_t*, const GameParams&) {}
 
@@ -327,13 +327,13 @@ struct LeducN {
 // S0: board c0..c4 6 bits each; S1: ptr:5 rc:3 (5) have_raised:3 (8) not_raise_num:5 (11) use_prev:1 (16) over:1 (31)
 // S2: raise_nums 4 x 3 (0..11), prev_raise_nums 4 x 3 (12..23) (the reset obs shows the previous game's, game.py:98)
 template <int NP>
-struct LimitN {
+struct LimitN : GameDefaults {
     static_assert(NP >= 3 && NP <= 22, "limit: 3..22 players (2P + 5 <= 52 dealt cards)");
     static constexpr int OBS = 72, A = 4, P = NP, LB = 1, WORDS = NP + 3, ACTION_BYTES = 1, NB = 3;
-    static constexpr bool RING = true, RAW_OBS = false, PAYOFF_DRAWS = true;
+    static constexpr bool RAW_OBS = false, PAYOFF_DRAWS = true;
     static constexpr int SCRATCH_WORDS = 0;
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100, STAGE_RF = 120;
-    static constexpr int RESTAGE_B = 8, MIN_WAVES = NP <= 10 ? 3 : 2, EPW = 64, REFILL_K = 2;
+    static constexpr int STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100, STAGE_RF = 120;
+    static constexpr int RESTAGE_B = 8, MIN_WAVES = NP <= 10 ? 3 : 2, EPW = 64;
     enum { CALL = 0, RAISE = 1, FOLD = 2, CHECK = 3 };
     __device__ __forceinline__ void bind(uint32_t*, const GameParams&) {}
 
@@ -478,13 +478,13 @@ struct LimitN {
 //     dealer drawn:1 (29) over:1 (31); S2: round pot + 1 (0 = the live pot; cs_nolimit.h round_pot). The stack is
 //     chips_for_each - in (not stored).
 template <int NP>
-struct NolimitN {
+struct NolimitN : GameDefaults {
     static_assert(NP >= 3 && NP <= 22, "no-limit: 3..22 players (2P + 5 <= 52 dealt cards)");
     static constexpr int OBS = 54, A = 5, P = NP, LB = 1, WORDS = NP + 3, ACTION_BYTES = 1, NB = 14;
-    static constexpr bool RING = true, RAW_OBS = true, PAYOFF_DRAWS = true;
+    static constexpr bool RAW_OBS = true, PAYOFF_DRAWS = true;
     static constexpr int SCRATCH_WORDS = 0;
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100, STAGE_RF = 100;
-    static constexpr int RESTAGE_B = 8, MIN_WAVES = NP <= 10 ? 3 : 2, EPW = 64, REFILL_K = 2;
+    static constexpr int STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100, STAGE_RF = 100;
+    static constexpr int RESTAGE_B = 8, MIN_WAVES = NP <= 10 ? 3 : 2, EPW = 64;
     enum { FOLD = 0, CHECK_CALL = 1, RAISE_HALF_POT = 2, RAISE_POT = 3, ALL_IN = 4 };
     enum { ALIVE = 0, FOLDED = 1, ALLIN = 2 };
 

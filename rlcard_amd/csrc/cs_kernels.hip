@@ -1,9 +1,9 @@
 // cs_kernels.hip -- lockstep env kernels for gfx950 (one lane = one env, one wave = 64 consecutive envs).
 //
-// The kernel skeleton (cs_skeleton.h) instantiated for the heads-up hold'em games, Blackjack and DouDizhu's seeding;
-// 3..22-player hold'em is instantiated in cs_holdem_n*.hip, the Blackjack shoe in cs_blackjack_shoe.hip. find_game
-// maps a game id and cs_config to the launch table entry (cs_engine.h GameOps) of its type; this is the one place
-// that decides it, and cs_abi.cpp asks once per handle.
+// The kernel skeleton (cs_skeleton.h) instantiated for the heads-up hold'em games and Blackjack; 3..22-player hold'em
+// is instantiated in cs_holdem_n*.hip, the Blackjack shoe in cs_blackjack_shoe.hip. find_game maps a game id and
+// cs_config to the launch table entry (cs_engine.h GameOps) of its type; this is the one place that decides it, and
+// cs_abi.cpp asks once per handle.
 #include "cs_skeleton.h"
 #include "cs_leduc.h"
 #include "cs_limit.h"
@@ -13,8 +13,7 @@
 
 namespace cs {
 
-// DouDizhu: its own kernels (cs_doudizhu.hip: a wave per env, env-major state, two 624-word MT blocks per env) behind
-// the skeleton's k_seed
+// DouDizhu: its own kernels (cs_doudizhu.hip: a wave per env, env-major state, two 624-word MT blocks per env)
 static const GameOps* ddz_ops()
 {
     static const GameOps ops = [] {
@@ -29,7 +28,7 @@ static const GameOps* ddz_ops()
         info.rng_period = 2 * 624;
         info.game_words = ddz::WORDS;
         info.envs_per_wave = 2;   // k_rollout2: one env per half-wave
-        return GameOps{seed_g<ddz::SeedView>, ddz::launch_reset, ddz::launch_step, ddz::launch_observe,
+        return GameOps{ddz::launch_seed, ddz::launch_reset, ddz::launch_step, ddz::launch_observe,
                        ddz::launch_rollout, info, 0, 2 * 624, false, true};
     }();
     return &ops;

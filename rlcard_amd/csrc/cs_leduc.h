@@ -20,20 +20,18 @@
 
 namespace cs {
 
-struct Leduc {
+struct Leduc : GameDefaults {
     // (no deal queue: drawing deals ahead, as Limit / No-limit do, measured slower here -- profiles/EXPERIMENTS.md)
     static constexpr int OBS = 36, A = 4, P = 2, LB = 1, WORDS = 2, ACTION_BYTES = 1;
     static constexpr int NB = 2;  // obs bitmap words
-    static constexpr bool RING = true;          // MT stream as the byte ring (cs_ring.h)
     static constexpr bool RAW_OBS = false;
     static constexpr int SCRATCH_WORDS = 0;
-    // MT staging (see MtLaneT)
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 64, STAGE_PAD = 4, STAGE_R = 12;
+    // the rollout's staged LDS rows (cs_device.h STAGE_LDS, Stage)
+    static constexpr int STAGE_W = 64, STAGE_PAD = 4, STAGE_R = 12;
     static constexpr int STAGE_RF = 24;   // batch restage threshold (ring_restage_wave): 24 > 40 > 56
     static constexpr int RESTAGE_B = 4;   // lanes restaged per pass (loads in flight): 4 > 8 > 1
     static constexpr int MIN_WAVES = 6;   // rollout waves per SIMD the register budget must allow
     static constexpr int EPW = 64;        // rollout envs per wave (lane_ctx)
-    static constexpr int REFILL_K = 1;    // refills are rare here, and K = 2 costs 12 VGPRs = 1 wave/SIMD
     __device__ __forceinline__ void bind(uint32_t*, const GameParams&) {}
     enum { CALL = 0, RAISE = 1, FOLD = 2, CHECK = 3 };
 

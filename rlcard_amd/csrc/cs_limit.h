@@ -263,23 +263,21 @@ constexpr int DQ_CB = HOLDEM_DQ == 8 ? 4 : HOLDEM_DQ == 4 ? 3 : 2;   // count bi
 constexpr int DQ_XB = 2 * DQ_CB - 1;                                // first bit after count and head
 static_assert(DQ_XB + 2 + 2 * HOLDEM_DQ <= 32, "deal queue header fits a word");
 
-struct Limit {
+struct Limit : GameDefaults {
     static constexpr int GW = 4;                        // game words; the deal queue follows
     static constexpr int DQ = HOLDEM_DQ;
     static constexpr int OBS = 72, A = 4, P = 2, LB = 1, WORDS = GW + HOLDEM_DQ_WORDS, ACTION_BYTES = 1;
     static constexpr int NB = 3;
-    static constexpr bool RING = true;          // MT stream as the byte ring (cs_ring.h)
     static constexpr bool RAW_OBS = false;
     static constexpr int SCRATCH_WORDS = 0;
-    // MT staging (see MtLaneT)
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100;
+    // the rollout's staged LDS rows (cs_device.h STAGE_LDS, Stage)
+    static constexpr int STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100;
     static constexpr int STAGE_RF = 120;  // batch restage threshold (ring_restage_wave): 2.70 -> 2.65 ms per 128 steps
     static constexpr int RESTAGE_B = 8;   // lanes restaged per pass (loads in flight)
     static constexpr int MIN_WAVES = 4;   // 4 waves/SIMD (LDS-bound with the 8-deal queue; at a 4-deal queue 5 beat 4
                                           // and 6, which spilled 40 VGPRs)
     static constexpr int EPW = 32;   // rollout envs per wave: 262 144 envs need half-full waves (lane_ctx)
-    static constexpr bool LANE_OPAQUE = false;   // k_rollout: lane id not made opaque per step (cs_skeleton.h LaneOpaque)
-    static constexpr int REFILL_K = 2;   // stale blocks twisted per pass (see mt_refill_wave)
+    static constexpr bool LANE_OPAQUE = false;   // k_rollout: lane id not made opaque per step (cs_device.h GameDefaults)
     __device__ __forceinline__ void bind(uint32_t*, const GameParams&) {}
     enum { CALL = 0, RAISE = 1, FOLD = 2, CHECK = 3 };
 

@@ -36,23 +36,21 @@
 
 namespace cs {
 
-struct Nolimit {
+struct Nolimit : GameDefaults {
     static constexpr int GW = 4;                        // game words; the deal queue follows (cs_limit.h)
     static constexpr int DQ = HOLDEM_DQ;
     static constexpr int OBS = 54, A = 5, P = 2, LB = 1, WORDS = GW + HOLDEM_DQ_WORDS, ACTION_BYTES = 1;
     static constexpr int NB = 14;               // raw obs bytes, four per word (RowWriterRaw)
-    static constexpr bool RING = true;          // MT stream as the byte ring (cs_ring.h)
     static constexpr bool RAW_OBS = true;
     static constexpr int SCRATCH_WORDS = 0;
     // MT staging and launch shape as limit hold'em (same deal: ~72 draws per game)
-    static constexpr int STAGE_MODE = STAGE_LDS, STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100;
+    static constexpr int STAGE_W = 128, STAGE_PAD = 8, STAGE_R = 100;
     static constexpr int STAGE_RF = 100;  // batch restage threshold (ring_restage_wave) = STAGE_R (120 the same)
     static constexpr int RESTAGE_B = 8;
     static constexpr int MIN_WAVES = 4;   // LDS-bound at 4 blocks per CU with the 8-deal queue
     static constexpr int EPW = 32;
-    static constexpr bool LANE_OPAQUE = false;   // k_rollout: lane id not made opaque per step (cs_skeleton.h LaneOpaque)
-    static constexpr bool REWARD_OPAQUE = true;  // k_rollout: keeps the reward rows' nontemporal hint (RewardOpaque)
-    static constexpr int REFILL_K = 2;
+    static constexpr bool LANE_OPAQUE = false;   // k_rollout: lane id not made opaque per step (cs_device.h GameDefaults)
+    static constexpr bool REWARD_OPAQUE = true;  // k_rollout: keeps the reward rows' nontemporal hint (GameDefaults)
     enum { FOLD = 0, CHECK_CALL = 1, RAISE_HALF_POT = 2, RAISE_POT = 3, ALL_IN = 4 };
     enum { ALIVE = 0, FOLDED = 1, ALLIN = 2 };
 

@@ -1,7 +1,7 @@
 // cs_ring.h -- the per-env MT19937 stream of the lane-per-env games as a ring of tempered low BYTES.
 //
 // Every draw of Leduc / Limit / No-limit Hold'em / Blackjack is numpy's random_interval(max <= 52), which reads only
-// the low 8 bits of a tempered output word (cs_device.h, MtLaneT). So the stream does not need to be kept as words:
+// the low 8 bits of a tempered output word (cs_device.h, STAGE_NONE / STAGE_LDS). So the stream does not need to be kept as words:
 // per env the engine holds
 //   wbuf[624]  u32       the untempered state words of the LATEST generated block L (the only input of the next twist)
 //   ring[S][624] u8      the low bytes of the tempered outputs of blocks L-S+1 .. L, block b in slot b % S
@@ -35,7 +35,7 @@ constexpr int RING_SLOTS = RING_SLOTS_HOST;
 static_assert(RING_SLOTS == 4 || RING_SLOTS == 8 || RING_SLOTS == 16, "ring slots: a power of two, position < 2^14");
 constexpr uint32_t SLOT_MASK = (uint32_t)RING_SLOTS - 1u;
 constexpr int RING_GEN = RING_SLOTS - 1;        // blocks generated per refill
-constexpr uint32_t RING = RING_SLOTS * MT_N;    // ring bytes: 2 496 (4 slots) / 4 992 (8 slots)
+constexpr uint32_t RING = RING_SLOTS * MT_N;    // ring bytes: 9 984 (2 496 at 4 slots, 4 992 at 8)
 static_assert(RING_ENV_WORDS_HOST == MT_N + RING_SLOTS * MT_N / 4, "host and device agree on the ring footprint");
 constexpr int RING_ENV_WORDS = RING_ENV_WORDS_HOST;   // u32 per env in the mt buffer: wbuf + the ring bytes
 constexpr uint32_t CTL_POS_MASK = 0x3FFFu;   // ctl bits 0..13: ring position
@@ -49,15 +49,6 @@ constexpr uint32_t CTL_IDLE = (uint32_t)(RING_GEN - 1) << CTL_LAT_SHIFT;
 __device__ __forceinline__ uint32_t shfl(uint32_t v, int src_lane)
 {
     return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v);
-}
-
-// numpy's twist (genrand_int32's reload), in place: mt[k] only reads mt[k+1], mt[k+397] (not yet rewritten) and the
-// already-new mt[k-227]
-__device__ inline void mt_twist_inplace(uint32_t* mt)
-{
-    for (int k = 0; k < MT_N - MT_M; k++) mt[k] = mt_mix(mt[k], mt[k + 1], mt[k + MT_M]);
-    for (int k = MT_N - MT_M; k < MT_N - 1; k++) mt[k] = mt_mix(mt[k], mt[k + 1], mt[k + MT_M - MT_N]);
-    mt[MT_N - 1] = mt_mix(mt[MT_N - 1], mt[0], mt[MT_M - 1]);
 }
 
 // bytes of one block (low byte of every tempered word) into ring slot `slot`, one lane
@@ -148,7 +139,7 @@ __device__ __forceinline__ void twist_regs(const uint32_t (&o)[10], uint32_t (&n
 __device__ __forceinline__ uint32_t ring_ld(const gu32* p) { return *p; }
 __device__ __forceinline__ void ring_st(gu32* p, uint32_t v) { *p = v; }
 
-// Wave-cooperative refill of one env: blocks L+1..L+3 from wbuf (block L, slot lat). All 64 lanes must call.
+// Wave-cooperative refill of one env: blocks L+1..L+RING_GEN from wbuf (block L, slot lat). All 64 lanes must call.
 __device__ __forceinline__ void ring_gen_wave(gu32* wbuf, uint32_t lat, int lane, uint32_t phx = 0)
 {
     if (phx) {   // Philox mode: 117 chunks over the 64 lanes, then the block counter (read by every lane first)
@@ -180,7 +171,7 @@ __device__ __forceinline__ void ring_gen_wave(gu32* wbuf, uint32_t lat, int lane
         if (c < 9 || lane < 48) ring_st(wbuf + 64 * c + lane, o[c]);
 }
 
-// One lane's view of its env's byte ring. MODE as MtLaneT: STAGE_NONE reads the ring in HBM per draw; STAGE_LDS
+// One lane's view of its env's byte ring. MODE (cs_device.h): STAGE_NONE reads the ring in HBM per draw; STAGE_LDS
 // reads the lane's staged LDS row (ring_restage_wave), HBM only past its end.
 template <int MODE = STAGE_NONE>
 struct RingLane {

@@ -18,45 +18,6 @@ namespace cs {
 constexpr int BLOCK = 256;
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;
 
-__device__ inline void mt_init_by_array(uint32_t* mt, const uint32_t* key, int klen)
-{
-    uint32_t prev = 19650218u;
-    mt[0] = prev;
-    for (int i = 1; i < MT_N; i++) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        mt[i] = prev;
-    }
-    int i = 1, j = 0;
-    prev = mt[0];
-    for (int k = MT_N; k; k--) {
-        const uint32_t v = (mt[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
-        mt[i] = v;
-        prev = v;
-        i++;
-        j++;
-        if (i >= MT_N) { mt[0] = mt[MT_N - 1]; prev = mt[0]; i = 1; }
-        if (j >= klen) j = 0;
-    }
-    for (int k = MT_N - 1; k; k--) {
-        const uint32_t v = (mt[i] ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;
-        mt[i] = v;
-        prev = v;
-        i++;
-        if (i >= MT_N) { mt[0] = mt[MT_N - 1]; prev = mt[0]; i = 1; }
-    }
-    mt[0] = 0x80000000u;
-}
-
-// k_rollout: the lane id made opaque at every step (per game, G::LANE_OPAQUE, default on). Round 5, same box: Limit
-// 8.18 -> 8.07 ms and No-limit 9.33 -> 9.10 without it, Blackjack 20.62 -> 20.89 and Leduc even
-template <class G, class = void>
-struct LaneOpaque {
-    static constexpr bool value = true;
-};
-template <class G>
-struct LaneOpaque<G, std::void_t<decltype(G::LANE_OPAQUE)>> {
-    static constexpr bool value = G::LANE_OPAQUE;
-};
 struct LaneCtx {
     int lane, wid;
     int64_t env, wave_first;
@@ -72,7 +33,7 @@ __device__ __forceinline__ LaneCtx lane_ctx(int64_t n)
     LaneCtx c;
     c.lane = threadIdx.x & (WAVE - 1);
     c.wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);   // wave-uniform: wave_first lives in SGPRs
-    const int64_t bx = (int64_t)blockIdx.x;   // (XCD-aware block order, cs_device.h xcd_block: +2 % for Leduc)
+    const int64_t bx = (int64_t)blockIdx.x;   // plain block order (cs_device.h xcd_block measured slower for Leduc)
     c.wave_first = (bx * WAVES_PER_BLOCK + c.wid) * EPW;
     c.env = c.wave_first + c.lane;
     const int64_t left = n - c.wave_first;
@@ -92,7 +53,7 @@ __device__ __forceinline__ RingLane<MODE> ring_lane(uint32_t* mt, const uint32_t
 }
 
 // end-of-step refill (flag bit 0: skipped, every block crossing takes the in-lane serial path -- a test variant)
-template <class G, class M>
+template <class M>
 __device__ __forceinline__ void refill(M& m, int lane, int flags)
 {
     if (!(flags & 1)) ring_refill_wave(m, lane);
@@ -139,20 +100,6 @@ __device__ __forceinline__ void write_obs_direct(uint8_t* o, const uint32_t (&bi
     }
 }
 
-// games whose obs rows are one-hot with SPARSE_K known positions (observe_pos) write them with row_write_sparse
-template <class G, class = void>
-struct SparseObs : std::false_type {};
-template <class G>
-struct SparseObs<G, std::void_t<decltype(G::SPARSE_K)>> : std::bool_constant<(G::SPARSE_K > 0)> {};
-template <class G, class = void>
-struct SparseK {   // positions per sparse row (1 where the game has none: a placeholder array)
-    static constexpr int value = 1;
-};
-template <class G>
-struct SparseK<G, std::void_t<decltype(G::SPARSE_K)>> {
-    static constexpr int value = G::SPARSE_K > 0 ? G::SPARSE_K : 1;
-};
-
 template <class G>
 __device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, uint64_t lg)
 {
@@ -160,24 +107,12 @@ __device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, uint64_t
     for (int k = 0; k < G::LB; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg >> (8 * k)));
 }
 
-// the 8-B reward row's value made opaque before its nontemporal store (per game, G::REWARD_OPAQUE, default off):
-// without it the optimizer may split the store back into two float stores and drop the nontemporal hint on the way
-// (No-limit's rollout); with it where the hint survives anyway (Leduc, Limit) the step schedules worse (Leduc 4.23 ->
-// 4.48 ms, round 5)
-template <class G, class = void>
-struct RewardOpaque {
-    static constexpr bool value = false;
-};
-template <class G>
-struct RewardOpaque<G, std::void_t<decltype(G::REWARD_OPAQUE)>> {
-    static constexpr bool value = G::REWARD_OPAQUE;
-};
 template <class G>
 __device__ __forceinline__ void emit_reward(float* reward, int64_t row, const float (&r)[G::P])
 {
     if constexpr (G::P == 2) {
         uint64_t v = (uint64_t)__float_as_uint(r[0]) | (uint64_t)__float_as_uint(r[1]) << 32;
-        if constexpr (RewardOpaque<G>::value) asm volatile("" : "+v"(v));
+        if constexpr (G::REWARD_OPAQUE) asm volatile("" : "+v"(v));
         out_store((uint64_t*)(reward + row * 2), v);
     } else {
 #pragma unroll
@@ -197,35 +132,17 @@ template <class G, int ROWS = WAVE>
 struct ObsLds {
     static constexpr int WORDS = obs_lds_words<G, ROWS>();
 };
-template <int W, int PAD, int ROWS, bool LDS>
-struct StageBytesOf {
-    static constexpr int value = 16;
-};
-template <int W, int PAD, int ROWS>
-struct StageBytesOf<W, PAD, ROWS, true> {
-    static constexpr int value = Stage<W, PAD, ROWS>::BYTES;
-};
 template <class G>
-struct StageBytes {
-    static constexpr int value = StageBytesOf<G::STAGE_W, G::STAGE_PAD, G::EPW, G::STAGE_MODE == STAGE_LDS>::value;
+struct StageBytes {   // a wave's staged rows in the rollout's LDS
+    static constexpr int value = Stage<G::STAGE_W, G::STAGE_PAD, G::EPW>::BYTES;
     // the staged-byte scans read one dword past their last staged byte (RingLane::interval, draw_intervals)
-    static_assert(G::STAGE_MODE != STAGE_LDS || G::STAGE_PAD >= 4, "stage rows need a pad of at least a dword");
+    static_assert(G::STAGE_PAD >= 4, "stage rows need a pad of at least a dword");
 };
-// batch restage threshold (ring_restage_wave): the game's STAGE_RF, else its STAGE_R (restage exactly the needy lanes)
-template <class G, class = void>
-struct StageRF {
-    static constexpr int value = G::STAGE_R;
-};
+// restage after the refill: STAGE_R starts one, STAGE_RF (>= STAGE_R) picks the lanes it takes (ring_restage_wave)
 template <class G>
-struct StageRF<G, std::void_t<decltype(G::STAGE_RF)>> {
-    static constexpr int value = G::STAGE_RF;
-};
-// restage after the refill, per the game's staging mode (see MtLaneT)
-template <class G, class M>
-__device__ __forceinline__ void restage(M& m, uint8_t* area, int lane, bool valid)
+__device__ __forceinline__ void restage(RingLane<STAGE_LDS>& m, uint8_t* area, int lane, bool valid)
 {
-    if constexpr (G::STAGE_MODE == STAGE_LDS)
-        ring_restage_wave<G::STAGE_W, G::STAGE_PAD, G::STAGE_R, G::RESTAGE_B, StageRF<G>::value>(m, area, lane, valid);
+    ring_restage_wave<G::STAGE_W, G::STAGE_PAD, G::STAGE_R, G::RESTAGE_B, G::STAGE_RF>(m, area, lane, valid);
 }
 template <class G>
 struct Scratch {   // per-lane LDS words of games that keep state in LDS (blackjack); one word per wave otherwise
@@ -236,24 +153,16 @@ __device__ __forceinline__ uint32_t* scratch_of(uint32_t* wave_area, int lane)
 {
     return G::SCRATCH_WORDS > 0 ? wave_area + lane : nullptr;
 }
-// Env.get_payoffs at the step that ends the game: games whose judge may draw from the env's stream (N-player hold'em's
-// odd split remainders, limitholdem/judger.py:80-83) take the lane's RNG
-template <class G, class = void>
-struct PayoffDraws {
-    static constexpr bool value = false;
-};
-template <class G>
-struct PayoffDraws<G, std::void_t<decltype(G::PAYOFF_DRAWS)>> {
-    static constexpr bool value = G::PAYOFF_DRAWS;
-};
+// Env.get_payoffs at the step that ends the game (PAYOFF_DRAWS: the judge takes the lane's RNG)
 template <class G, class Rng>
 __device__ __forceinline__ void game_payoffs(G& g, float (&r)[G::P], Rng& rng)
 {
-    if constexpr (PayoffDraws<G>::value) g.payoffs(r, rng);
+    if constexpr (G::PAYOFF_DRAWS) g.payoffs(r, rng);
     else g.payoffs(r);
 }
 
-// reset of the env's game through its deal queue where the game has one (cs_dq.h)
+// Game.init_game for k_reset / k_step. A forwarding layer only, and kept: with game_reset_hbm called directly the
+// compiler orders a few operands of k_reset<Nolimit> and k_step<Nolimit> differently (same instructions and registers)
 template <class G, class Rng>
 __device__ __forceinline__ void game_reset(G& g, Rng& rng, uint32_t* st, int64_t n, int64_t env)
 {
@@ -280,74 +189,41 @@ __device__ __forceinline__ void step_record(const StepRecord& rec, const uint32_
 #define CS_SMEM(G) CS_SMEM_ROWS(G, WAVE)
 
 // ------------------------------------------------------------------------------------------------------------------
+// Seeding, a lane per env (env first + i takes key i): S0 = init_by_array(key) in wbuf, then the env's first blocks
+// generated in place, and a finished game, so the next reset / step deals
 template <class G>
 __global__ __launch_bounds__(BLOCK) void k_seed(uint32_t* mt, uint32_t* ctl, uint32_t* st, int64_t n,
                                                  const uint32_t* keys, const int32_t* klen, int64_t first,
-                                                 int64_t count, int flags, GameParams prm)
+                                                 int64_t count, int /* kernel flags: none applies */, GameParams prm)
 {
     __shared__ uint32_t scr[WAVES_PER_BLOCK][Scratch<G>::WORDS];
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const bool valid = i < count;
+    if (i >= count) return;
     const int64_t env = first + i;
-    if constexpr (G::RING) {   // byte ring: S0 = init_by_array(key) in wbuf, blocks 0..RING_GEN-1 generated in place
-        if (!valid) return;
-        uint32_t* wbuf = mt + env * RING_ENV_WORDS;
-        const int kl = klen[i] == 2 ? 2 : 1;                    // validated on the host; never trust it here
-        const uint32_t phx = prm.rng_mode == CS_RNG_PHILOX ? CTL_PHILOX : 0u;
-        const uint32_t kb = seed_blocks(env);                  // blocks 0..kb-1 now (cs_ring.h seed_blocks)
-        if (phx) {   // Philox byte stream: key = the init_by_array key, blocks 0..kb-1 into slots 0..kb-1, counter kb
-            wbuf[0] = 0u;
-            wbuf[1] = keys[2 * i];
-            wbuf[2] = kl == 2 ? keys[2 * i + 1] : 0u;
-            ring_gen_philox((gu32*)wbuf, SLOT_MASK, 0, 1, (int)kb);
-            wbuf[0] = kb;
-        } else {
-            mt_init_by_array(wbuf, keys + 2 * i, kl);
-            for (uint32_t b = 0; b < kb; b++) {     // numpy's first draws: block 0 = twist(S0)
-                mt_twist_inplace(wbuf);
-                ring_bytes_serial(wbuf, (uint8_t*)(wbuf + MT_N), b);
-            }
-        }
-        G g;
-        g.bind(scratch_of<G>(scr[threadIdx.x / WAVE], lane), prm);
-        g.blank();
-        g.store(st, n, env);
-        if constexpr (DqOf<G>::value > 0) st[(int64_t)G::GW * n + env] = 0u;   // empty deal queue
-        ctl[env] = 0u | (kb - 1u) << CTL_LAT_SHIFT | phx;   // position 0, latest block in slot kb - 1
-        return;
-    }
-    MtLane m;
-    m.init(mt, 0, 0);
-    // Philox mode (doudizhu's word layout, cs_doudizhu.hip WaveMt): the key in words 0..1, draw count 0 in word 2
-    const bool phx = prm.rng_mode == CS_RNG_PHILOX;   // uniform
-    if (valid) {
-        uint32_t* base = mt + env * MT_WORDS;
-        const int kl = klen[i] == 2 ? 2 : 1;                    // validated on the host; never trust it here
-        if (phx) {
-            base[0] = keys[2 * i];
-            base[1] = kl == 2 ? keys[2 * i + 1] : 0u;
-            base[2] = 0u;
-        } else {
-            mt_init_by_array(base + MT_N, keys + 2 * i, kl);    // S0 in block 1 (scratch)
-            mt_twist_serial(base + MT_N, base);                 // block 0 = twist(S0): numpy's first draws
-            m.base = base;
-            m.stale = 1;                                        // block 1 = twist(block 0), refilled below
-        }
-        G g;
-        g.bind(scratch_of<G>(scr[threadIdx.x / WAVE], lane), prm);
-        g.blank();
-        g.store(st, n, env);
-    }
-    if (!phx) {
-        if (flags & 1) {
-            if (valid) mt_twist_serial(m.base, m.base + MT_N);
-            m.stale = 0;
-        } else {
-            mt_refill_wave(m, lane);
+    uint32_t* wbuf = mt + env * RING_ENV_WORDS;
+    const int kl = klen[i] == 2 ? 2 : 1;                    // validated on the host; never trust it here
+    const uint32_t phx = prm.rng_mode == CS_RNG_PHILOX ? CTL_PHILOX : 0u;
+    const uint32_t kb = seed_blocks(env);                  // blocks 0..kb-1 now (cs_ring.h seed_blocks)
+    if (phx) {   // Philox byte stream: key = the init_by_array key, blocks 0..kb-1 into slots 0..kb-1, counter kb
+        wbuf[0] = 0u;
+        wbuf[1] = keys[2 * i];
+        wbuf[2] = kl == 2 ? keys[2 * i + 1] : 0u;
+        ring_gen_philox((gu32*)wbuf, SLOT_MASK, 0, 1, (int)kb);
+        wbuf[0] = kb;
+    } else {
+        mt_init_by_array(wbuf, keys + 2 * i, kl);
+        for (uint32_t b = 0; b < kb; b++) {     // numpy's first draws: block 0 = twist(S0)
+            mt_twist_inplace(wbuf);
+            ring_bytes_serial(wbuf, (uint8_t*)(wbuf + MT_N), b);
         }
     }
-    if (valid) ctl[env] = phx ? CTL_PHILOX : 0u;
+    G g;
+    g.bind(scratch_of<G>(scr[threadIdx.x / WAVE], lane), prm);
+    g.blank();
+    g.store(st, n, env);
+    if constexpr (DqOf<G>::value > 0) st[(int64_t)G::GW * n + env] = 0u;   // empty deal queue
+    ctl[env] = 0u | (kb - 1u) << CTL_LAT_SHIFT | phx;   // position 0, latest block in slot kb - 1
 }
 
 template <class G>
@@ -364,7 +240,7 @@ __global__ __launch_bounds__(BLOCK) void k_reset(uint32_t* mt, uint32_t* ctl, ui
         g.load(st, n, c.env);   // the Game object outlives init_game (limit-holdem's raise history, :98/:101)
         game_reset(g, m, st, n, c.env);
     }
-    refill<G>(m, c.lane, flags & 1);
+    refill(m, c.lane, flags & 1);
     uint32_t bits[G::NB];
     const int p = g.current();
     g.observe(p, bits);
@@ -410,7 +286,7 @@ __global__ __launch_bounds__(BLOCK) void k_step(uint32_t* mt, uint32_t* ctl, uin
             if (done) game_payoffs(g, r, m);
         }
     }
-    refill<G>(m, c.lane, flags & 1);
+    refill(m, c.lane, flags & 1);
     uint32_t bits[G::NB];
     const int p = g.current();
     g.observe(p, bits);
@@ -474,16 +350,6 @@ static_assert(std::is_standard_layout<RolloutArgs>::value && std::is_trivially_c
 static_assert(offsetof(RolloutArgs, mt) == 0 && alignof(RolloutArgs) == 8 && sizeof(RolloutArgs) % 8 == 0,
               "RolloutArgs: first kernarg at offset 0, 8-byte aligned");
 
-// games with rule policies (G::MAX_POLICY, G::rule_action: cs_leduc.h, cs_limit.h)
-template <class G, class = void>
-struct MaxPolicy {
-    static constexpr int value = 0;
-};
-template <class G>
-struct MaxPolicy<G, std::void_t<decltype(G::MAX_POLICY)>> {
-    static constexpr int value = G::MAX_POLICY;
-};
-
 // The rollout. POL = false (cs_rollout) plays the uniform-random policy; POL = true (cs_rollout_policy) is a second
 // instantiation in which seat p plays byte p of args.seats (CS_POLICY_*). Everything the policy path adds sits inside
 // `if constexpr (POL)`, so the random rollout -- tuned to its register budget, see the comments below -- compiles from
@@ -507,24 +373,20 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
     CS_SMEM_ROWS(G, G::EPW);
     __shared__ __attribute__((aligned(16))) uint8_t stage[WAVES_PER_BLOCK][StageBytes<G>::value];
     const LaneCtx c = lane_ctx<G::EPW>(n);
-    RingLane<G::STAGE_MODE> m = ring_lane<G::STAGE_MODE>(mt, ctl, c);
+    RingLane<STAGE_LDS> m = ring_lane<STAGE_LDS>(mt, ctl, c);
     // MT staging needs both blocks valid at every restage, i.e. the cooperative refill (flag bit 0 off);
     // flag bit 1 disables it (one global load per draw) for A/B runs and fallback-path tests
     const bool staged = !(flags & 3);
-    constexpr bool persist = G::STAGE_MODE == STAGE_LDS;
-    uint8_t* rows = nullptr;
-    if constexpr (persist) {
-        // the staged rows left by the previous launch stay valid while ctl bit 17 is set (single-step kernels and
-        // seeding rewrite ctl without it)
-        rows = sbuf + c.wave_first * G::STAGE_W;
-        if (staged) {
-            if (c.valid && ((ctl[c.env] >> 17) & 1u)) {
-                const uint32_t w = sctl[c.env];
-                m.sp = w & 0xFFFFu;
-                m.sn = w >> 16;
-            }
-            stage_rows_copy<G::STAGE_W, G::STAGE_PAD>(stage[c.wid], rows, c.lane, c.nvalid, true);
+    // the staged rows left by the previous launch stay valid while ctl bit 17 is set (single-step kernels and
+    // seeding rewrite ctl without it)
+    uint8_t* rows = sbuf + c.wave_first * G::STAGE_W;
+    if (staged) {
+        if (c.valid && ((ctl[c.env] >> 17) & 1u)) {
+            const uint32_t w = sctl[c.env];
+            m.sp = w & 0xFFFFu;
+            m.sn = w >> 16;
         }
+        stage_rows_copy<G::STAGE_W, G::STAGE_PAD>(stage[c.wid], rows, c.lane, c.nvalid, true);
     }
     // the deal queues of the wave's envs for the launch in LDS (DQW consecutive words per lane: odd stride)
     constexpr int DQ = DqOf<G>::value, DQW = DqOf<G>::words;
@@ -547,7 +409,7 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
             else g.reset(m);
         }
     }
-    refill<G>(m, c.lane, flags & 1);
+    refill(m, c.lane, flags & 1);
     if (staged) restage<G>(m, stage[c.wid], c.lane, c.valid);
     PolicyRng pol;
     const uint64_t genv0 = args.env_base + (uint64_t)c.env;   // the policy counter's env id
@@ -557,7 +419,7 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
         // from it instead of held across the step -- at 6 waves per SIMD (80 VGPRs) the held copies were spilled, and
         // a spill reload waits on every store the wave has in flight (vmcnt)
         LaneCtx cl = c;
-        if constexpr (LaneOpaque<G>::value) {
+        if constexpr (G::LANE_OPAQUE) {
             int ol = c.lane;
             asm volatile("" : "+v"(ol));
             cl.lane = ol;
@@ -580,8 +442,9 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
         // slower on every torch allocation, profiles/EXPERIMENTS.md)
         const uint32_t pr = pol.at(seed, genv0, t0 + (uint64_t)t, t == 0);
         int a;
+        static_assert(G::A <= 32, "the policy pick takes a 32-bit legal mask");
         if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
-        else a = G::A <= 32 ? pick_legal32((uint32_t)lg, pr) : pick_legal(lg, pr);
+        else a = pick_legal32((uint32_t)lg, pr);
         if constexpr (POL) {
             // the seats' policies are one word of the argument block (a scalar load); the acting seat's byte picks
             // between the random pick above -- always made, at cs_rollout's counter, so random seats play the same
@@ -591,10 +454,10 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
             a = pid == (uint32_t)CS_POLICY_RANDOM ? a : ra;
         }
 #if !CS_PROF_NO_OBS
-        if constexpr (SparseObs<G>::value) {
-            uint32_t pos[SparseK<G>::value];
+        if constexpr (G::SPARSE_K > 0) {
+            uint32_t pos[G::SPARSE_K];
             const uint32_t tail = g.observe_pos(p, pos);
-            row_write_sparse<G::OBS, G::EPW, SparseK<G>::value, G::RAW_OBS>(
+            row_write_sparse<G::OBS, G::EPW, G::SPARSE_K, G::RAW_OBS>(
                 lds[c.wid], pos, obs + (rowbase + c.wave_first) * G::OBS, cl.lane, c.nvalid, !(flags & 4), tail);
         } else {
             emit_obs<G, G::EPW>(lds[c.wid], bits, obs, rowbase + c.wave_first, flags, cl);
@@ -646,15 +509,13 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
             }
             if (c.valid && done) dq_reset(g, m, q);
         }
-        refill<G>(m, cl.lane, flags & 1);
+        refill(m, cl.lane, flags & 1);
         if (staged) restage<G>(m, stage[c.wid], cl.lane, c.valid);
     }
     bool keep = false;
-    if constexpr (persist) {
-        if (staged) {
-            stage_rows_copy<G::STAGE_W, G::STAGE_PAD>(stage[c.wid], rows, c.lane, c.nvalid, false);
-            keep = true;
-        }
+    if (staged) {
+        stage_rows_copy<G::STAGE_W, G::STAGE_PAD>(stage[c.wid], rows, c.lane, c.nvalid, false);
+        keep = true;
     }
     if (c.valid) {
         g.store(st, n, c.env);
@@ -705,20 +566,20 @@ static hipError_t seed_g(const Buffers& b, const uint32_t* keys, const int32_t* 
                          hipStream_t s)
 {
     hipLaunchKernelGGL(k_seed<G>, grid_for(count), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, keys, klen, first,
-                       count, b.serial_refill, params_of(b));
+                       count, b.kernel_flags, params_of(b));
     return hipGetLastError();
 }
 template <class G>
 static hipError_t reset_g(const Buffers& b, const cs_step_out& o, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_reset<G>, grid_for(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, o, b.serial_refill,
+    hipLaunchKernelGGL(k_reset<G>, grid_for(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, o, b.kernel_flags,
                        params_of(b), b.rec);
     return hipGetLastError();
 }
 template <class G>
 static hipError_t step_g(const Buffers& b, const int32_t* a, const cs_step_out& o, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_step<G>, grid_for(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, a, o, b.serial_refill,
+    hipLaunchKernelGGL(k_step<G>, grid_for(b.n), dim3(BLOCK), 0, s, b.mt, b.ctl, b.state, b.n, a, o, b.kernel_flags,
                        params_of(b), b.rec);
     return hipGetLastError();
 }
@@ -732,7 +593,7 @@ template <class G>
 static hipError_t rollout_g(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
                             const cs_traj_out& o, hipStream_t s)
 {
-    const RolloutArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, params_of(b), b.sctl, b.sbuf, T, b.serial_refill};
+    const RolloutArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, params_of(b), b.sctl, b.sbuf, T, b.kernel_flags};
     hipLaunchKernelGGL(k_rollout<G>, grid_for(b.n, G::EPW), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
@@ -741,7 +602,7 @@ template <class G>
 static hipError_t rollout_policy_g(const Buffers& b, int32_t T, uint64_t seed, uint64_t t0, uint64_t env_base,
                                    uint32_t seats, const cs_traj_out& o, hipStream_t s)
 {
-    const RolloutArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, params_of(b), b.sctl, b.sbuf, T, b.serial_refill,
+    const RolloutArgs a{b.mt, b.ctl, b.state, b.n, seed, t0, env_base, o, params_of(b), b.sctl, b.sbuf, T, b.kernel_flags,
                         seats, 0u};
     hipLaunchKernelGGL((k_rollout<G, true>), grid_for(b.n, G::EPW), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
@@ -771,22 +632,19 @@ static void fill_info(cs_game_info* info)
     info->envs_per_wave = G::EPW;
 }
 
-template <class G>
-static int32_t stage_bytes_of() { return G::STAGE_MODE == STAGE_LDS ? G::STAGE_W : 0; }
-
 // The launch table entry (cs_engine.h) of skeleton game G. Naming it instantiates the five kernels for G (and the two
 // policy kernels of a game with rule policies).
 template <class G>
 static const GameOps* ops_of()
 {
     static const GameOps ops = [] {
-        GameOps o{seed_g<G>, reset_g<G>, step_g<G>, observe_g<G>, rollout_g<G>, {}, stage_bytes_of<G>(),
+        GameOps o{seed_g<G>, reset_g<G>, step_g<G>, observe_g<G>, rollout_g<G>, {}, G::STAGE_W,
                   RING_ENV_WORDS, false, false};
         fill_info<G>(&o.info);
-        if constexpr (MaxPolicy<G>::value > 0) {   // naming them instantiates the two policy kernels for G
+        if constexpr (G::MAX_POLICY > 0) {   // naming them instantiates the two policy kernels for G
             o.rollout_policy = rollout_policy_g<G>;
             o.policy_actions = policy_actions_g<G>;
-            o.max_policy = MaxPolicy<G>::value;
+            o.max_policy = G::MAX_POLICY;
         }
         return o;
     }();

@@ -155,7 +155,7 @@ __device__ __forceinline__ uint4 row_chunk(uintptr_t cs, uintptr_t a, uintptr_t 
 {
     uint4 v;
     typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(1))) const v4u g4;   // global, not flat (see cs_device.h to_global)
+    typedef __attribute__((address_space(1))) const v4u g4;   // global, not flat (see cs_device.h gu32)
     typedef __attribute__((address_space(1))) const uint8_t g1;
     if (cs + 16 <= e) {
         const v4u t = *(g4*)cs;
