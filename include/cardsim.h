@@ -71,8 +71,8 @@ typedef struct {
  * cs_state_* functions); a consumer built against this header checks cs_abi_version() >= CS_ABI_VERSION before
  * calling cs_game_info_get, which writes sizeof(cs_game_info) bytes of this version. Functions added without a
  * layout change keep the version (cs_rollout_policy, cs_policy_actions, cs_payoff_sums; cs_qnet_values,
- * cs_qnet_actions, the cs_replay_* functions, cs_dqn_targets): a consumer that may meet an older library looks the
- * symbol up. */
+ * cs_qnet_actions, the cs_replay_* functions, cs_dqn_targets; cs_pnet_probs, cs_nfsp_scratch_bytes, cs_nfsp_actions,
+ * the cs_reservoir_* functions): a consumer that may meet an older library looks the symbol up. */
 #define CS_ABI_VERSION 3
 
 /* Outputs of reset/step/observe, all device pointers, one row per env:
@@ -364,6 +364,53 @@ int  cs_replay_gather(cs_replay* r, const int64_t* idx, int64_t B, const cs_repl
 int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* next_legal, const float* reward,
                    const void* done, int64_t B, int32_t num_actions, float gamma, float* target, int32_t* best,
                    void* stream);
+
+/* ---- NFSP agent (rlcard/agents/nfsp_agent.py) -------------------------------------------------------------------
+ * The average-policy network is a cs_qnet descriptor read as Linear/ReLU (AveragePolicyNetwork with its BatchNorm
+ * folded: rlcard_amd.agents.AveragePolicyNetwork.folded()). Its head restates NFSPAgent._act and remove_illegal in
+ * fp32: p[a] = expf(l[a] - max) / sum over every action, illegal entries zeroed, the legal ones divided by their sum,
+ * or 1 / count each where that sum is exactly 0. Refusals are cs_qnet_values'.
+ *
+ * probs f32 [rows][num_actions] for `rows` observation rows (obs, legal as in cs_qnet_values), 0 where illegal. */
+int cs_pnet_probs(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* probs,
+                  void* stream);
+/* NFSPAgent.step for `rows` rows, each in its own mode (mode u8 [rows], DEVICE): a row with mode != 0 (best_response)
+ * gets exactly cs_qnet_actions' action of that row under (eps, seed, t, row_base) from qnet; a row with mode 0
+ * (average_policy) gets an action sampled from pnet's probabilities: with r = Philox keyed by seed on (row_base + row,
+ * t) -- the epsilon draw's call -- u = (r[2] >> 8) * 2^-24, the first legal action a in id order with u < c_a, c the
+ * running fp32 sum of the row's probabilities (the last legal action if rounding leaves u >= c). Done rows and rows
+ * with an empty mask get -1. mode NULL: every row average policy (qnet may be NULL then). probs (may be NULL) f32
+ * [rows][num_actions] takes the average-policy rows' probabilities; the other rows are left untouched. The rows are
+ * compacted by mode into one index list per network on the device (no host synchronisation) in `scratch`: DEVICE
+ * memory of cs_nfsp_scratch_bytes(rows) bytes (a negative CS_E_* code on failure), 256-byte aligned, the caller's
+ * (unused when mode is NULL). */
+int64_t cs_nfsp_scratch_bytes(int64_t rows);
+int cs_nfsp_actions(cs_handle* h, const cs_qnet* qnet, const cs_qnet* pnet, const void* obs, const void* legal,
+                    const void* done, const void* mode, int64_t rows, float eps, uint64_t seed, uint64_t t,
+                    uint64_t row_base, int32_t* actions, float* probs, void* scratch, void* stream);
+
+/* Reservoir buffer of a handle's envs on the device (nfsp_agent.py ReservoirBuffer of (info_state, action_probs)).
+ * Only best-response steps are stored and their action_probs are one-hot, so a slot holds state u8 [obs_dim] and the
+ * action id. Games with more than 8 actions (DouDizhu) are CS_E_UNSUPPORTED. */
+typedef struct cs_reservoir cs_reservoir;
+int  cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reservoir** out);
+void cs_reservoir_destroy(cs_reservoir* r);
+/* Offer the rows of a trajectory window (cs_rollout layout [T][n]; obs, player and action are read) to the buffer:
+ * the candidates are the rows with player < num_players, that seat in seat_mask and mode[t][e] != 0 (mode u8 [T][n],
+ * DEVICE), in (t, env) order. Candidate number pos of the push has stream index k = add_calls + pos and is added as
+ * ReservoirBuffer.add adds its k-th element: to slot k while k < capacity; afterwards to slot j = (x * (k + 1)) >> 64,
+ * x = r[0] | r[1] << 32 of Philox keyed by seed on (k, 0), if j < capacity, and dropped otherwise. The buffer after the
+ * push is the sequential algorithm's (of several candidates on one slot the last one stays). add_calls advances by
+ * the number of candidates. */
+int  cs_reservoir_push(cs_reservoir* r, int32_t T, const cs_traj_out* traj, const void* mode, uint32_t seat_mask,
+                       void* stream);
+/* add_calls = candidates ever offered, size = min(add_calls, capacity). HOST out, synchronous. */
+int  cs_reservoir_size(cs_reservoir* r, int64_t* size, int64_t* add_calls);
+/* idx i64 [B] (DEVICE), slot indices in [0, size) (outside: the caller's error, clamped) -> state f32 [B][obs_dim],
+ * probs f32 [B][num_actions] one-hot (either may be NULL). B <= 0: no-op. */
+int  cs_reservoir_gather(cs_reservoir* r, const int64_t* idx, int64_t B, float* state, float* probs, void* stream);
+/* ReservoirBuffer.clear: empty, add_calls 0. */
+int  cs_reservoir_clear(cs_reservoir* r, void* stream);
 
 /* Copy the packed state words of env `env` (state_words u32, HOST buffer) -- the raw fields behind
  * Env.get_state()['raw_obs'] / get_perfect_information for single-env compatibility and debugging. Synchronous.

@@ -72,12 +72,16 @@ SYMBOLS = ('cs_game_info_get', 'cs_create', 'cs_destroy', 'cs_seed', 'cs_reset',
            'cs_dmc_select', 'cs_last_error', 'cs_version', 'cs_abi_version', 'cs_state_bytes', 'cs_state_save',
            'cs_state_load', 'cs_rollout_policy', 'cs_policy_actions', 'cs_payoff_sums',
            'cs_qnet_values', 'cs_qnet_actions', 'cs_replay_create', 'cs_replay_destroy', 'cs_replay_push',
-           'cs_replay_drop_pending', 'cs_replay_size', 'cs_replay_gather', 'cs_dqn_targets')
+           'cs_replay_drop_pending', 'cs_replay_size', 'cs_replay_gather', 'cs_dqn_targets',
+           'cs_pnet_probs', 'cs_nfsp_scratch_bytes', 'cs_nfsp_actions', 'cs_reservoir_create', 'cs_reservoir_destroy',
+           'cs_reservoir_push', 'cs_reservoir_size', 'cs_reservoir_gather', 'cs_reservoir_clear')
 # symbols an older library build may lack (A/B builds loaded with CARDSIM_LIB); callers check hasattr(lib(), name)
 OPTIONAL = ('cs_traj_probe', 'cs_state_bytes', 'cs_state_save', 'cs_state_load', 'cs_rollout_policy',
             'cs_policy_actions', 'cs_payoff_sums', 'cs_qnet_values', 'cs_qnet_actions', 'cs_replay_create',
             'cs_replay_destroy', 'cs_replay_push', 'cs_replay_drop_pending', 'cs_replay_size', 'cs_replay_gather',
-            'cs_dqn_targets')
+            'cs_dqn_targets', 'cs_pnet_probs', 'cs_nfsp_scratch_bytes', 'cs_nfsp_actions', 'cs_reservoir_create',
+            'cs_reservoir_destroy', 'cs_reservoir_push', 'cs_reservoir_size', 'cs_reservoir_gather',
+            'cs_reservoir_clear')
 
 POLICY_RANDOM, POLICY_RULE_V1, POLICY_RULE_V2 = 0, 1, 2   # CS_POLICY_* (rlcard_amd.models gives them names)
 
@@ -128,6 +132,20 @@ def lib():
         L.cs_replay_size.argtypes = [vp, vp, vp]
         L.cs_replay_gather.argtypes = [vp, vp, i64, C.POINTER(ReplayBatch), vp]
         L.cs_dqn_targets.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp]
+    if hasattr(L, 'cs_nfsp_actions'):   # (the NFSP entry points, added the same way)
+        f32 = C.c_float
+        L.cs_pnet_probs.argtypes = [vp, C.POINTER(QNet), vp, vp, i64, vp, vp]
+        L.cs_nfsp_scratch_bytes.argtypes = [i64]
+        L.cs_nfsp_scratch_bytes.restype = i64
+        L.cs_nfsp_actions.argtypes = [vp, C.POINTER(QNet), C.POINTER(QNet), vp, vp, vp, vp, i64, f32, u64, u64, u64, vp,
+                                      vp, vp, vp]
+        L.cs_reservoir_create.argtypes = [vp, i64, u64, C.POINTER(vp)]
+        L.cs_reservoir_destroy.argtypes = [vp]
+        L.cs_reservoir_destroy.restype = None
+        L.cs_reservoir_push.argtypes = [vp, i32, C.POINTER(TrajOut), vp, C.c_uint32, vp]
+        L.cs_reservoir_size.argtypes = [vp, vp, vp]
+        L.cs_reservoir_gather.argtypes = [vp, vp, i64, vp, vp, vp]
+        L.cs_reservoir_clear.argtypes = [vp, vp]
     L.cs_transitions.argtypes = [vp, i32, C.POINTER(TrajOut), C.POINTER(TransOut), vp]
     L.cs_legal_lists.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.cs_action_features.argtypes = [vp, vp, i64, vp, vp]
@@ -160,8 +178,8 @@ def lib():
             raise CardsimError('%s implements ABI version %d, this binding needs %d' % (LIB_PATH, L.cs_abi_version(),
                                                                                      ABI_VERSION))
     for name in SYMBOLS:
-        if name not in ('cs_destroy', 'cs_dmc_destroy', 'cs_replay_destroy', 'cs_last_error', 'cs_version',
-                        'cs_abi_version'):
+        if name not in ('cs_destroy', 'cs_dmc_destroy', 'cs_replay_destroy', 'cs_reservoir_destroy',
+                        'cs_nfsp_scratch_bytes', 'cs_last_error', 'cs_version', 'cs_abi_version'):
             if name in OPTIONAL and not hasattr(L, name):   # older A/B builds (CARDSIM_LIB) lack it
                 continue
             getattr(L, name).restype = C.c_int

@@ -32,6 +32,39 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def descriptor(wb, device):
+    """[(W, b)] per Linear (float64 numpy, BatchNorm folded) -> the cs_qnet descriptor (_abi.QNet): float32 tensors on
+    `device`, kept alive by the descriptor's `tensors`."""
+    if not 1 <= len(wb) - 1 <= 4:
+        raise ValueError('the Q-network kernels take 1..4 hidden layers, got %d' % (len(wb) - 1))
+    net = _abi.QNet()
+    net.in_dim = wb[0][0].shape[1]
+    net.num_hidden = len(wb) - 1
+    net.num_actions = wb[-1][0].shape[0]
+    net.tensors = []
+    for k, (W, b) in enumerate(wb):
+        if k < net.num_hidden:
+            net.hidden[k] = W.shape[0]
+        Wt = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float32)).to(device)
+        bt = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(device)
+        net.tensors += [Wt, bt]
+        net.W[k], net.b[k] = Wt.data_ptr(), bt.data_ptr()
+    return net
+
+
+def fold_batchnorm(bn, linears):
+    """[(W, b)] per Linear as float64 numpy, the eval-mode BatchNorm1d `bn` folded into the first: with s = gamma /
+    sqrt(running_var + eps) and c = beta - running_mean * s, BatchNorm is x * s + c, so W0' = W0 * s (per input
+    column) and b0' = b0 + W0 . c."""
+    f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)   # noqa: E731
+    s = f64(bn.weight) / np.sqrt(f64(bn.running_var) + bn.eps)
+    c = f64(bn.bias) - f64(bn.running_mean) * s
+    out = [(f64(m.weight), f64(m.bias)) for m in linears]
+    W0, b0 = out[0]
+    out[0] = (W0 * s[None, :], b0 + W0 @ c)
+    return out
+
+
 class EstimatorNetwork(nn.Module):
     """Flatten -> BatchNorm1d -> (Linear -> Tanh) per entry of mlp_layers -> Linear to num_actions."""
 
@@ -104,15 +137,7 @@ class Estimator:
         """[(W, b)] per Linear as float64 numpy, the eval-mode BatchNorm folded into the first: with s = gamma /
         sqrt(running_var + eps) and c = beta - running_mean * s, BatchNorm is x * s + c, so W0' = W0 * s (per input
         column) and b0' = b0 + W0 . c."""
-        bn = self.qnet.fc_layers[1]
-        lin = [m for m in self.qnet.fc_layers if isinstance(m, nn.Linear)]
-        f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)   # noqa: E731
-        s = f64(bn.weight) / np.sqrt(f64(bn.running_var) + bn.eps)
-        c = f64(bn.bias) - f64(bn.running_mean) * s
-        out = [(f64(m.weight), f64(m.bias)) for m in lin]
-        W0, b0 = out[0]
-        out[0] = (W0 * s[None, :], b0 + W0 @ c)
-        return out
+        return fold_batchnorm(self.qnet.fc_layers[1], [m for m in self.qnet.fc_layers if isinstance(m, nn.Linear)])
 
     def _version(self):
         return tuple(t._version for t in self.qnet.state_dict().values()) + (str(self.device),)
@@ -124,21 +149,7 @@ class Estimator:
         ver = self._version()
         if self._folded is not None and self._folded[0] == ver:
             return self._folded[1]
-        wb = self.folded_weights()
-        if not 1 <= len(wb) - 1 <= 4:
-            raise ValueError('the Q-network kernels take 1..4 hidden layers, got %d' % (len(wb) - 1))
-        net = _abi.QNet()
-        net.in_dim = wb[0][0].shape[1]
-        net.num_hidden = len(wb) - 1
-        net.num_actions = wb[-1][0].shape[0]
-        net.tensors = []
-        for k, (W, b) in enumerate(wb):
-            if k < net.num_hidden:
-                net.hidden[k] = W.shape[0]
-            Wt = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float32)).to(self.device)
-            bt = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)).to(self.device)
-            net.tensors += [Wt, bt]
-            net.W[k], net.b[k] = Wt.data_ptr(), bt.data_ptr()
+        net = descriptor(self.folded_weights(), self.device)
         self._folded = (ver, net)
         return net
 
@@ -562,7 +573,7 @@ class DQNCollector:
         """steps_per_feed env steps -> the trajectory ([T][N] rows with final_obs; reused by the next call)."""
         v, tr, st = self.vec, self.traj, self.state
         for k in range(self.steps):
-            acts = self.agent.step_vec(st, self.t, self.seed)
+            acts = self._agent_actions(k, st)
             opp = self._opponent_actions(st)
             if opp is not None:
                 acts = torch.where(self.mine[st['player'].long()], acts, opp)
@@ -577,9 +588,17 @@ class DQNCollector:
             ended = st['done'].bool().unsqueeze(-1)
             for p in range(v.num_players):   # every seat's view of the finished games (Env.run's final states)
                 tr['final_obs'][k, :, p].copy_(torch.where(ended, v.observe(p, self._obs)['obs'], 0))
+            self._stepped(st)
             self.t += 1
         self.state = st
         return tr
+
+    def _agent_actions(self, k, state):
+        """the agent's actions for step k of the window"""
+        return self.agent.step_vec(state, self.t, self.seed)
+
+    def _stepped(self, state):
+        """after every env step, with the state it led to (NFSPCollector resamples the finished games' modes)"""
 
     def run(self, train_steps=None):
         """collect() + agent.feed_vec -> the losses of the train steps."""

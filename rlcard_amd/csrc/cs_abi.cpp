@@ -617,6 +617,163 @@ int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* 
     return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dqn_targets");
 }
 
+// ---- NFSP ---------------------------------------------------------------------------------------------------------
+int cs_pnet_probs(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* probs,
+                  void* stream)
+{
+    int r = qnet_check(h, net, obs, rows);
+    if (r != CS_OK) return r;
+    if (!probs) return fail(CS_E_INVALID, "null argument");
+    if (rows == 0) return CS_OK;
+    if ((r = set_device(h)) != CS_OK) return r;
+    hipError_t e = cs::launch_pnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0, 0, 0, nullptr,
+                                   probs, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_pnet_probs");
+}
+
+int64_t cs_nfsp_scratch_bytes(int64_t rows)
+{
+    if (rows < 0 || rows > 0x7FFFFFFF) return fail(CS_E_INVALID, "rows out of range");
+    size_t bytes = 0;
+    hipError_t e = cs::nfsp_scratch_bytes(rows > 0 ? rows : 1, &bytes);
+    return e == hipSuccess ? (int64_t)bytes : fail_hip(e, "cs_nfsp_scratch_bytes");
+}
+
+int cs_nfsp_actions(cs_handle* h, const cs_qnet* qnet, const cs_qnet* pnet, const void* obs, const void* legal,
+                    const void* done, const void* mode, int64_t rows, float eps, uint64_t seed, uint64_t t,
+                    uint64_t row_base, int32_t* actions, float* probs, void* scratch, void* stream)
+{
+    int r = qnet_check(h, pnet, obs, rows);
+    if (r != CS_OK) return r;
+    if (mode && (r = qnet_check(h, qnet, obs, rows)) != CS_OK) return r;
+    if (!actions || (mode && !scratch)) return fail(CS_E_INVALID, "null argument");
+    if (rows == 0) return CS_OK;
+    if ((r = set_device(h)) != CS_OK) return r;
+    hipError_t e;
+    if (!mode)
+        e = cs::launch_pnet(*pnet, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done, rows, seed, t,
+                            row_base, actions, probs, (hipStream_t)stream);
+    else
+        e = cs::launch_nfsp_actions(*qnet, *pnet, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done,
+                                    (const uint8_t*)mode, rows, eps, seed, t, row_base, actions, probs, scratch,
+                                    (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_nfsp_actions");
+}
+
+struct cs_reservoir {
+    cs_handle* h;
+    cs::Reservoir r;
+    void* mem;          // one allocation for the slots, the occupant words and the counter
+    size_t tail;        // bytes from the occupant words to the end of mem (what clear zeroes)
+    int32_t* pos;       // scan output of a push, [entries] (grown on demand)
+    int64_t entries;
+    void* scan_tmp;
+    size_t scan_bytes;
+};
+
+int cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reservoir** out)
+{
+    if (!h || !out) return fail(CS_E_INVALID, "null argument");
+    *out = nullptr;
+    if (capacity <= 0) return fail(CS_E_INVALID, "capacity must be positive");
+    const cs_game_info& info = h->ops->info;
+    if (info.num_actions > 8) return fail(CS_E_UNSUPPORTED, "cs_reservoir: games of at most 8 actions");
+    int rc = set_device(h);
+    if (rc != CS_OK) return rc;
+    const int64_t O = info.obs_dim, cap = capacity;
+    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
+    const int64_t o_st = 0, o_act = o_st + al(cap * O), o_occ = o_act + al(cap * 4), o_calls = o_occ + al(cap * 8),
+                  total = o_calls + 256;
+    cs_reservoir* p = new (std::nothrow) cs_reservoir();
+    if (!p) return fail(CS_E_INVALID, "out of host memory");
+    hipError_t e = hipMalloc(&p->mem, (size_t)total);
+    if (e != hipSuccess) { delete p; return fail_hip(e, "cs_reservoir_create"); }
+    uint8_t* m = (uint8_t*)p->mem;
+    e = hipMemset(m, 0, (size_t)total);
+    if (e != hipSuccess) { (void)hipFree(p->mem); delete p; return fail_hip(e, "cs_reservoir_create"); }
+    p->h = h;
+    p->r = cs::Reservoir{cap, (int32_t)O, info.num_players, info.num_actions, info.action_bytes, seed, m + o_st,
+                         (int32_t*)(m + o_act), (unsigned long long*)(m + o_occ), (int64_t*)(m + o_calls)};
+    p->tail = (size_t)(total - o_occ);
+    p->pos = nullptr;
+    p->entries = 0;
+    p->scan_tmp = nullptr;
+    p->scan_bytes = 0;
+    *out = p;
+    return CS_OK;
+}
+
+void cs_reservoir_destroy(cs_reservoir* r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->h->device);
+    if (r->mem) (void)hipFree(r->mem);
+    if (r->pos) (void)hipFree(r->pos);
+    if (r->scan_tmp) (void)hipFree(r->scan_tmp);
+    delete r;
+}
+
+int cs_reservoir_push(cs_reservoir* r, int32_t T, const cs_traj_out* traj, const void* mode, uint32_t seat_mask,
+                      void* stream)
+{
+    if (!r || !traj || !mode) return fail(CS_E_INVALID, "null argument");
+    if (!traj->obs || !traj->player || !traj->action)
+        return fail(CS_E_INVALID, "cs_reservoir_push needs the trajectory's obs, player and action");
+    if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
+    const int64_t entries = (int64_t)T * r->h->b.n + 1;
+    if (entries > 0x7FFFFFFF)
+        return fail(CS_E_INVALID, "cs_reservoir_push: window too large (T * n must stay below 2^31)");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    if (entries > r->entries) {
+        if (r->pos) (void)hipFree(r->pos);
+        r->pos = nullptr;
+        r->entries = 0;
+        hipError_t e = hipMalloc((void**)&r->pos, (size_t)entries * sizeof(int32_t));
+        if (e != hipSuccess) return fail_hip(e, "cs_reservoir_push");
+        r->entries = entries;
+    }
+    hipError_t e = cs::launch_reservoir_push(r->r, T, r->h->b.n, (const uint8_t*)traj->obs,
+                                             (const uint8_t*)traj->player, traj->action, (const uint8_t*)mode,
+                                             seat_mask, r->pos, &r->scan_tmp, &r->scan_bytes, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_push");
+}
+
+int cs_reservoir_size(cs_reservoir* r, int64_t* size, int64_t* add_calls)
+{
+    if (!r || (!size && !add_calls)) return fail(CS_E_INVALID, "null argument");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    int64_t t = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&t, r->r.add_calls, sizeof(int64_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail_hip(e, "cs_reservoir_size");
+    if (add_calls) *add_calls = t;
+    if (size) *size = t < r->r.cap ? t : r->r.cap;
+    return CS_OK;
+}
+
+int cs_reservoir_gather(cs_reservoir* r, const int64_t* idx, int64_t B, float* state, float* probs, void* stream)
+{
+    if (!r) return fail(CS_E_INVALID, "null argument");
+    if (B <= 0) return CS_OK;
+    if (!idx) return fail(CS_E_INVALID, "null argument");
+    if (B > 0x7FFFFFFF / 32) return fail(CS_E_INVALID, "B out of range");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    hipError_t e = cs::launch_reservoir_gather(r->r, idx, B, state, probs, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_gather");
+}
+
+int cs_reservoir_clear(cs_reservoir* r, void* stream)
+{
+    if (!r) return fail(CS_E_INVALID, "null argument");
+    int rc = set_device(r->h);
+    if (rc != CS_OK) return rc;
+    hipError_t e = hipMemsetAsync(r->r.occ, 0, r->tail, (hipStream_t)stream);
+    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_clear");
+}
+
 int cs_traj_probe(cs_handle* h, int32_t T, const cs_traj_out* out, void* stream)
 {
     if (!h || !out) return fail(CS_E_INVALID, "null argument");

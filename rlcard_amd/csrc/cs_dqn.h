@@ -27,6 +27,35 @@ int64_t qnet_lds_bytes(const cs_qnet& net);
 hipError_t launch_qnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
                        float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
                        hipStream_t s);
+// the descriptor read as Linear/ReLU with the average-policy head (softmax, remove_illegal, a sampled action)
+hipError_t launch_pnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
+                       uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* probs, hipStream_t s);
+// mode u8 [rows]: 1 the Q-network's epsilon-greedy action, 0 the average policy's sampled one; the rows are compacted
+// into one list per network in `scratch` (nfsp_scratch_bytes(rows) bytes, 256-B aligned) and each network runs over
+// its list
+hipError_t nfsp_scratch_bytes(int64_t rows, size_t* bytes);
+hipError_t launch_nfsp_actions(const cs_qnet& qnet, const cs_qnet& pnet, const uint8_t* obs, const uint8_t* legal,
+                               const uint8_t* done, const uint8_t* mode, int64_t rows, float eps, uint64_t seed,
+                               uint64_t t, uint64_t row_base, int32_t* actions, float* probs, void* scratch,
+                               hipStream_t s);
+
+// Reservoir buffer of a handle (cs_reservoir, cs_nfsp.hip): `cap` slots of (state, action id)
+struct Reservoir {
+    int64_t cap;
+    int32_t O, P, A, abytes;    // obs bytes, players, actions, bytes per trajectory action
+    uint64_t seed;              // key of the replacement draws
+    uint8_t* st;                // [cap][O] state
+    int32_t* act;               // [cap] action id (the one-hot action_probs row)
+    unsigned long long* occ;    // [cap] stream index + 1 of the slot's occupant, 0 = empty
+    int64_t* add_calls;         // [1] candidates ever offered (ReservoirBuffer._add_calls)
+};
+// pos: [T * n + 1] i32 scratch of the push (grown by the caller)
+hipError_t launch_reservoir_push(const Reservoir& r, int32_t T, int64_t n, const uint8_t* obs, const uint8_t* player,
+                                 const void* action, const uint8_t* mode, uint32_t seat_mask, int32_t* pos, void** tmp,
+                                 size_t* tmp_bytes, hipStream_t s);
+hipError_t launch_reservoir_gather(const Reservoir& r, const int64_t* idx, int64_t B, float* state, float* probs,
+                                   hipStream_t s);
+
 // code: [n * P + T * n + 1] i32, pos: the same length (scratch of the push, grown by the caller)
 hipError_t launch_replay_push(const Buffers& b, const ReplayRing& r, int32_t T, const cs_traj_out& tr,
                               uint32_t seat_mask, int32_t* code, int32_t* pos, void** tmp, size_t* tmp_bytes,

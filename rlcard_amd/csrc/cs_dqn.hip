@@ -16,6 +16,11 @@
 //                       registers while the previous stage's FMAs run. A net with a layer wider than 64 units runs two
 //                       waves per block, one per tile of the layer. The output layer (<= 8 actions) is one pass with a
 //                       lane per row, its weights staged once, and stays in registers for the mask and the argmax.
+//                     The same kernel is NFSP's average-policy network (rlcard/agents/nfsp_agent.py): a template on the
+//                     hidden activation (tanh | ReLU), the head (masked argmax + epsilon draw | softmax, remove_illegal
+//                     and a sampled action) and an optional row list; the tiling and the staging are shared.
+//   k_row_lists       cs_nfsp_actions: the rows of each mode compacted into an index list (positions from a prefix sum
+//                     over the mode bytes), so that each network's instantiation runs over its own rows only.
 //   k_replay_index / k_replay_write / k_replay_carry
 //                     reorganize (rlcard/utils/utils.py:153-179) of a trajectory window into the replay ring, with the
 //                     rows whose game runs past the window carried as one pending row per (env, seat) and completed by
@@ -50,15 +55,35 @@ __device__ __forceinline__ void qnet_tile_load(const float* __restrict__ W, int 
     }
 }
 
+// ACT: the hidden layers' activation; HEAD: what the output lane does with its row. LIST: the block's rows are
+// idx[row0 ..] of the first *count entries of a row list (launch_nfsp_actions) -- whole obs rows are gathered, and the
+// row's mask, done byte, draw key and outputs are those of row idx[r]; without it row r is row r.
+enum { Q_TANH = 0, Q_RELU = 1 };
+enum { Q_ARGMAX = 0, Q_SOFTMAX = 1 };
+
+template <int ACT>
+__device__ __forceinline__ float qnet_act(float x)
+{
+    if constexpr (ACT == Q_RELU) return fmaxf(x, 0.f);
+    else return tanhf(x);
+}
+
+template <int ACT, int HEAD, bool LIST>
 __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, int szB, const uint8_t* __restrict__ obs,
                                                 const uint8_t* __restrict__ legal, const uint8_t* __restrict__ done,
                                                 int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base,
-                                                int32_t* __restrict__ actions, float* __restrict__ q)
+                                                int32_t* __restrict__ actions, float* __restrict__ q,
+                                                const int32_t* __restrict__ idx, const int32_t* __restrict__ count)
 {
     extern __shared__ __attribute__((aligned(16))) float q_lds[];
     const int tid = (int)threadIdx.x, BT = (int)blockDim.x, lane = tid & (WAVE - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), NW = BT >> 6;   // this wave of the block's 1 or 2
-    const int64_t row0 = (int64_t)blockIdx.x * QROWS, row = row0 + lane;
+    const int64_t row0 = (int64_t)blockIdx.x * QROWS;
+    if constexpr (LIST) {   // the grid covers `rows`; the list holds *count of them (every thread reads the same word,
+        rows = *count;      // so a block past the list leaves as one, before any barrier)
+        if (row0 >= rows) return;
+    }
+    const int64_t row = row0 + lane;
     const int D = net.in_dim, A = net.num_actions, NH = net.num_hidden;
     float* bufA = q_lds;                  // [szA][64]: the obs rows, then the outputs of layers 1, 3
     float* bufB = bufA + szA * QROWS;     // [szB][64]: the outputs of layers 0, 2
@@ -70,7 +95,8 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
         const uint8_t* src = obs + row0 * D;
         for (int j = tid; j < nb; j += BT) {
             const int r = j / D, u = j - r * D;
-            bufA[u * QROWS + r] = (float)src[j];
+            if constexpr (LIST) bufA[u * QROWS + r] = (float)obs[(int64_t)idx[row0 + r] * D + u];
+            else bufA[u * QROWS + r] = (float)src[j];
         }
     }
     const int lr = lane & 7, lo = lane >> 3;   // the lane's 8 rows (8 lr ..) and 8 output units (8 lo ..) of a tile
@@ -126,9 +152,10 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
                 const int o = ot + lo * 8 + j;
                 if (o < out) {
                     float* d = xout + o * QROWS + lr * 8;
-                    *(float4*)d = make_float4(tanhf(acc[j][0]), tanhf(acc[j][1]), tanhf(acc[j][2]), tanhf(acc[j][3]));
-                    *(float4*)(d + 4) =
-                        make_float4(tanhf(acc[j][4]), tanhf(acc[j][5]), tanhf(acc[j][6]), tanhf(acc[j][7]));
+                    *(float4*)d = make_float4(qnet_act<ACT>(acc[j][0]), qnet_act<ACT>(acc[j][1]),
+                                              qnet_act<ACT>(acc[j][2]), qnet_act<ACT>(acc[j][3]));
+                    *(float4*)(d + 4) = make_float4(qnet_act<ACT>(acc[j][4]), qnet_act<ACT>(acc[j][5]),
+                                                    qnet_act<ACT>(acc[j][6]), qnet_act<ACT>(acc[j][7]));
                 }
             }
         }
@@ -159,35 +186,84 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
         for (int j = 0; j < QOC; j++) acc[j] = fmaf(w[j], x, acc[j]);
     }
     if (row >= rows) return;
+    int64_t orow = row;   // the row the mask, the done byte, the draw key and the outputs belong to
+    if constexpr (LIST) orow = idx[row];
     const uint32_t all = (1u << A) - 1u;
-    const uint32_t mask = legal ? (uint32_t)legal[row] & all : all;   // A <= 8: one mask byte per row
-    if (q) {
+    const uint32_t mask = legal ? (uint32_t)legal[orow] & all : all;   // A <= 8: one mask byte per row
+    if constexpr (HEAD == Q_SOFTMAX) {
+        // AveragePolicyNetwork + NFSPAgent._act + remove_illegal: np.exp(log_softmax) over every action, the illegal
+        // entries zeroed, the rest divided by their sum (uniform over the legal actions where that sum underflowed)
+        float mx = acc[0];
+#pragma unroll
+        for (int k = 1; k < QOC; k++)
+            if (k < A) mx = fmaxf(mx, acc[k]);
+        float p[QOC], sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < QOC; k++) {
+            p[k] = k < A ? expf(acc[k] - mx) : 0.f;
+            sum += p[k];
+        }
+        float lsum = 0.f;
+#pragma unroll
+        for (int k = 0; k < QOC; k++) {
+            p[k] = (mask >> k) & 1u ? p[k] / sum : 0.f;
+            lsum += p[k];
+        }
+        const float uni = 1.0f / (float)__popc(mask);
 #pragma unroll
         for (int k = 0; k < QOC; k++)
-            if (k < A) q[row * A + k] = (mask >> k) & 1u ? acc[k] : -INFINITY;
-    }
-    if (!actions) return;
-    int best = -1;
-    float bv = 0.f;
+            if ((mask >> k) & 1u) p[k] = lsum == 0.f ? uni : p[k] / lsum;
+        if (q) {
 #pragma unroll
-    for (int k = 0; k < QOC; k++)
-        if (((mask >> k) & 1u) && (best < 0 || acc[k] > bv)) {
-            best = k;
-            bv = acc[k];
+            for (int k = 0; k < QOC; k++)
+                if (k < A) q[orow * A + k] = p[k];
         }
-    if (best >= 0 && eps > 0.f) {   // k_dmc_select's draw (cs_dmc.hip)
+        if (!actions) return;
+        // the first legal action whose running sum passes u (third Philox word: the epsilon draw takes the first two)
         uint32_t r[4];
-        philox4(seed, row_base + (uint64_t)row, t, r);
-        const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-        if (u < eps) {
-            int kth = (int)(((uint64_t)r[1] * (uint64_t)__popc(mask)) >> 32);
-            uint32_t m = mask;
-            while (kth-- > 0) m &= m - 1;
-            best = __builtin_ctz(m);
+        philox4(seed, row_base + (uint64_t)orow, t, r);
+        const float u = (float)(r[2] >> 8) * (1.0f / 16777216.0f);
+        int pick = -1, last = -1;
+        float c = 0.f;
+#pragma unroll
+        for (int k = 0; k < QOC; k++)
+            if ((mask >> k) & 1u) {
+                c = c + p[k];
+                last = k;
+                if (pick < 0 && u < c) pick = k;
+            }
+        if (pick < 0) pick = last;   // (rounding left the sum below u)
+        if (done && done[orow]) pick = -1;
+        actions[orow] = pick;
+    } else {
+        if (q) {
+#pragma unroll
+            for (int k = 0; k < QOC; k++)
+                if (k < A) q[orow * A + k] = (mask >> k) & 1u ? acc[k] : -INFINITY;
         }
+        if (!actions) return;
+        int best = -1;
+        float bv = 0.f;
+#pragma unroll
+        for (int k = 0; k < QOC; k++)
+            if (((mask >> k) & 1u) && (best < 0 || acc[k] > bv)) {
+                best = k;
+                bv = acc[k];
+            }
+        if (best >= 0 && eps > 0.f) {   // k_dmc_select's draw (cs_dmc.hip)
+            uint32_t r[4];
+            philox4(seed, row_base + (uint64_t)orow, t, r);
+            const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+            if (u < eps) {
+                int kth = (int)(((uint64_t)r[1] * (uint64_t)__popc(mask)) >> 32);
+                uint32_t m = mask;
+                while (kth-- > 0) m &= m - 1;
+                best = __builtin_ctz(m);
+            }
+        }
+        if (done && done[orow]) best = -1;
+        actions[orow] = best;
     }
-    if (done && done[row]) best = -1;
-    actions[row] = best;
 }
 
 static void qnet_sizes(const cs_qnet& net, int* szA, int* szB)
@@ -216,20 +292,104 @@ int64_t qnet_lds_bytes(const cs_qnet& net)
     return (((int64_t)a + b) * QROWS + qnet_waves(net) * QWT) * (int64_t)sizeof(float);
 }
 
-hipError_t launch_qnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
-                       float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
-                       hipStream_t s)
+template <int ACT, int HEAD, bool LIST>
+static hipError_t launch_net(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done,
+                             int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions,
+                             float* out, const int32_t* idx, const int32_t* count, hipStream_t s)
 {
     int szA, szB;
     qnet_sizes(net, &szA, &szB);
     const int64_t bytes = qnet_lds_bytes(net);
+    auto kern = k_qnet<ACT, HEAD, LIST>;
     if (bytes > 65536) {   // past the default limit of dynamic LDS (the [128, 128, ..] nets): raise this kernel's
-        hipError_t e = hipFuncSetAttribute((const void*)k_qnet, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_qnet, dim3((unsigned)((rows + QROWS - 1) / QROWS)), dim3(QROWS * qnet_waves(net)), (size_t)bytes, s, net, szA,
-                       szB, obs, legal, done, rows, eps, seed, t, row_base, actions, q);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + QROWS - 1) / QROWS)), dim3(QROWS * qnet_waves(net)),
+                       (size_t)bytes, s, net, szA, szB, obs, legal, done, rows, eps, seed, t, row_base, actions, out,
+                       idx, count);
     return hipGetLastError();
+}
+
+hipError_t launch_qnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
+                       float eps, uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* q,
+                       hipStream_t s)
+{
+    return launch_net<Q_TANH, Q_ARGMAX, false>(net, obs, legal, done, rows, eps, seed, t, row_base, actions, q, nullptr,
+                                               nullptr, s);
+}
+
+// the same descriptor read as Linear/ReLU with the average-policy head: probs (may be NULL) f32 [rows][A], actions
+// (may be NULL) the sampled ones
+hipError_t launch_pnet(const cs_qnet& net, const uint8_t* obs, const uint8_t* legal, const uint8_t* done, int64_t rows,
+                       uint64_t seed, uint64_t t, uint64_t row_base, int32_t* actions, float* probs, hipStream_t s)
+{
+    return launch_net<Q_RELU, Q_SOFTMAX, false>(net, obs, legal, done, rows, 0.f, seed, t, row_base, actions, probs,
+                                                nullptr, nullptr, s);
+}
+
+// ---- NFSP: each network on its own rows ------------------------------------------------------------------------------
+// Scratch of launch_nfsp_actions, all i32: pos [rows] (exclusive sum of the mode bytes), list0 [rows] (average-policy
+// rows, ascending), list1 [rows] (best-response rows), counts [2], then the scan's temporary storage.
+struct ModeFlag {
+    __host__ __device__ int32_t operator()(const uint8_t& m) const { return m ? 1 : 0; }
+};
+
+__global__ __launch_bounds__(QBLOCK) void k_row_lists(const uint8_t* __restrict__ mode, int64_t rows,
+                                                      const int32_t* __restrict__ pos, int32_t* __restrict__ list0,
+                                                      int32_t* __restrict__ list1, int32_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
+    if (i >= rows) return;
+    const int32_t ones = pos[i];   // mode-1 rows before row i
+    const bool br = mode[i] != 0;
+    if (br) list1[ones] = (int32_t)i;
+    else list0[i - ones] = (int32_t)i;
+    if (i == rows - 1) {
+        const int32_t c1 = ones + (br ? 1 : 0);
+        counts[0] = (int32_t)rows - c1;
+        counts[1] = c1;
+    }
+}
+
+static size_t nfsp_lists_bytes(int64_t rows)
+{
+    return (((size_t)rows * 3 + 2) * sizeof(int32_t) + 255) / 256 * 256;
+}
+
+hipError_t nfsp_scratch_bytes(int64_t rows, size_t* bytes)
+{
+    hipcub::TransformInputIterator<int32_t, ModeFlag, const uint8_t*> flags(nullptr, ModeFlag());
+    size_t need = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags, (int32_t*)nullptr, (int)rows, (hipStream_t)0);
+    if (e != hipSuccess) return e;
+    *bytes = nfsp_lists_bytes(rows) + need + 256;
+    return hipSuccess;
+}
+
+hipError_t launch_nfsp_actions(const cs_qnet& qnet, const cs_qnet& pnet, const uint8_t* obs, const uint8_t* legal,
+                               const uint8_t* done, const uint8_t* mode, int64_t rows, float eps, uint64_t seed,
+                               uint64_t t, uint64_t row_base, int32_t* actions, float* probs, void* scratch,
+                               hipStream_t s)
+{
+    int32_t* pos = (int32_t*)scratch;
+    int32_t* list0 = pos + rows;
+    int32_t* list1 = list0 + rows;
+    int32_t* counts = list1 + rows;
+    void* tmp = (uint8_t*)scratch + nfsp_lists_bytes(rows);
+    hipcub::TransformInputIterator<int32_t, ModeFlag, const uint8_t*> flags(mode, ModeFlag());
+    size_t need = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags, pos, (int)rows, s);
+    if (e != hipSuccess) return e;
+    if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, need, flags, pos, (int)rows, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_row_lists, dim3((unsigned)((rows + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, mode, rows, pos,
+                       list0, list1, counts);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    e = launch_net<Q_RELU, Q_SOFTMAX, true>(pnet, obs, legal, done, rows, 0.f, seed, t, row_base, actions, probs, list0,
+                                            counts, s);
+    if (e != hipSuccess) return e;
+    return launch_net<Q_TANH, Q_ARGMAX, true>(qnet, obs, legal, done, rows, eps, seed, t, row_base, actions, nullptr,
+                                              list1, counts + 1, s);
 }
 
 // ---- replay ring ---------------------------------------------------------------------------------------------------
