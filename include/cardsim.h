@@ -253,7 +253,9 @@ int cs_cfr_train(cs_handle* h, int32_t iterations, int64_t iteration0, double* p
  * The streams live in a ring of `slots` chunks per (env, player) in HBM. Chunk ids handed out by cs_dmc_fill must be
  * gathered (cs_dmc_gather) before the next cs_dmc_fill reuses their slots; rows that would overwrite a chunk still
  * held are dropped and flagged (cs_dmc_status). Needs slots * T >= T + the rows one fill adds per (env, player) +
- * the longest game's rows. */
+ * the longest game's rows.
+ * Lifetime of the buffers created on a handle (cs_dmc, cs_replay, cs_reservoir): a buffer may be destroyed after its
+ * handle; every other call on it needs the handle alive. */
 typedef struct cs_dmc cs_dmc;
 
 /* get_batch (utils.py:33-46) output, DEVICE pointers, [T][B] rows (any may be NULL):

@@ -5,6 +5,8 @@ There is no CPU fallback: if the library is missing, or no GPU is visible, calls
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get('CARDSIM_LIB', 'libcardsim.so'))   # CARDSIM_LIB: A/B builds only
 
@@ -62,26 +64,77 @@ class ReplayBatch(C.Structure):
                 ('next_legal', C.c_void_p), ('done', C.c_void_p)]
 
 
-# every symbol include/cardsim.h declares (tests check the library exports all of them)
-SYMBOLS = ('cs_game_info_get', 'cs_create', 'cs_destroy', 'cs_seed', 'cs_reset', 'cs_step', 'cs_observe',
-           'cs_rollout', 'cs_traj_probe', 'cs_transitions', 'cs_legal_lists', 'cs_action_features', 'cs_get_env_state',
-           'cs_set_env_state', 'cs_copy_env_state', 'cs_set_step_record', 'cs_env_rng_words', 'cs_copy_env_rng',
-           'cs_load_env_rng', 'cs_get_rng_ctl', 'cs_cfr_train', 'cs_debug_holdem_rank7', 'cs_debug_ddz_legal',
-           'cs_debug_set_serial_refill', 'cs_debug_set_kernel_flags',
-           'cs_dmc_create', 'cs_dmc_destroy', 'cs_dmc_fill', 'cs_dmc_gather', 'cs_dmc_status', 'cs_dmc_layer1',
-           'cs_dmc_select', 'cs_last_error', 'cs_version', 'cs_abi_version', 'cs_state_bytes', 'cs_state_save',
-           'cs_state_load', 'cs_rollout_policy', 'cs_policy_actions', 'cs_payoff_sums',
-           'cs_qnet_values', 'cs_qnet_actions', 'cs_replay_create', 'cs_replay_destroy', 'cs_replay_push',
-           'cs_replay_drop_pending', 'cs_replay_size', 'cs_replay_gather', 'cs_dqn_targets',
-           'cs_pnet_probs', 'cs_nfsp_scratch_bytes', 'cs_nfsp_actions', 'cs_reservoir_create', 'cs_reservoir_destroy',
-           'cs_reservoir_push', 'cs_reservoir_size', 'cs_reservoir_gather', 'cs_reservoir_clear')
-# symbols an older library build may lack (A/B builds loaded with CARDSIM_LIB); callers check hasattr(lib(), name)
-OPTIONAL = ('cs_traj_probe', 'cs_state_bytes', 'cs_state_save', 'cs_state_load', 'cs_rollout_policy',
-            'cs_policy_actions', 'cs_payoff_sums', 'cs_qnet_values', 'cs_qnet_actions', 'cs_replay_create',
-            'cs_replay_destroy', 'cs_replay_push', 'cs_replay_drop_pending', 'cs_replay_size', 'cs_replay_gather',
-            'cs_dqn_targets', 'cs_pnet_probs', 'cs_nfsp_scratch_bytes', 'cs_nfsp_actions', 'cs_reservoir_create',
-            'cs_reservoir_destroy', 'cs_reservoir_push', 'cs_reservoir_size', 'cs_reservoir_gather',
-            'cs_reservoir_clear')
+def _prototypes():
+    vp, i32, i64, u32, u64, f32, rc, P = (C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_int,
+                                          C.POINTER)
+    traj, net = P(TrajOut), P(QNet)
+    return {
+        'cs_game_info_get': (rc, [i32, P(Config), P(GameInfo)]),
+        'cs_create': (rc, [P(vp), i32, i64, i32, P(Config)]),
+        'cs_destroy': (None, [vp]),
+        'cs_seed': (rc, [vp, vp, vp, i64, i64, vp]),
+        'cs_reset': (rc, [vp, P(StepOut), vp]),
+        'cs_step': (rc, [vp, vp, P(StepOut), vp]),
+        'cs_observe': (rc, [vp, i32, P(StepOut), vp]),
+        'cs_rollout': (rc, [vp, i32, u64, u64, u64, traj, vp]),
+        'cs_rollout_policy': (rc, [vp, i32, u64, u64, u64, vp, traj, vp]),
+        'cs_policy_actions': (rc, [vp, i32, u64, u64, u64, vp, vp]),
+        'cs_payoff_sums': (rc, [vp, i32, traj, i32, vp, vp, vp, vp]),
+        'cs_traj_probe': (rc, [vp, i32, traj, vp]),
+        'cs_state_bytes': (rc, [vp, vp]),
+        'cs_state_save': (rc, [vp, vp, vp]),
+        'cs_state_load': (rc, [vp, vp, vp]),
+        'cs_transitions': (rc, [vp, i32, traj, P(TransOut), vp]),
+        'cs_legal_lists': (rc, [vp, vp, i64, vp, vp, vp, vp]),
+        'cs_action_features': (rc, [vp, vp, i64, vp, vp]),
+        'cs_cfr_train': (rc, [vp, i32, i64, vp, vp, vp, vp, vp]),
+        'cs_dmc_create': (rc, [vp, i32, i32, P(vp)]),
+        'cs_dmc_destroy': (None, [vp]),
+        'cs_dmc_fill': (rc, [vp, i32, traj, vp, i64, vp, vp]),
+        'cs_dmc_gather': (rc, [vp, i32, vp, i64, P(DmcBatch), vp]),
+        'cs_dmc_status': (rc, [vp, vp]),
+        'cs_dmc_layer1': (rc, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
+        'cs_dmc_select': (rc, [vp, vp, vp, vp, i64, f32, u64, u64, u64, vp, vp]),
+        'cs_qnet_values': (rc, [vp, net, vp, vp, i64, vp, vp]),
+        'cs_qnet_actions': (rc, [vp, net, vp, vp, vp, i64, f32, u64, u64, u64, vp, vp, vp]),
+        'cs_replay_create': (rc, [vp, i64, P(vp)]),
+        'cs_replay_destroy': (None, [vp]),
+        'cs_replay_push': (rc, [vp, i32, traj, u32, vp]),
+        'cs_replay_drop_pending': (rc, [vp, vp]),
+        'cs_replay_size': (rc, [vp, vp, vp]),
+        'cs_replay_gather': (rc, [vp, vp, i64, P(ReplayBatch), vp]),
+        'cs_dqn_targets': (rc, [vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp]),
+        'cs_pnet_probs': (rc, [vp, net, vp, vp, i64, vp, vp]),
+        'cs_nfsp_scratch_bytes': (i64, [i64]),
+        'cs_nfsp_actions': (rc, [vp, net, net, vp, vp, vp, vp, i64, f32, u64, u64, u64, vp, vp, vp, vp]),
+        'cs_reservoir_create': (rc, [vp, i64, u64, P(vp)]),
+        'cs_reservoir_destroy': (None, [vp]),
+        'cs_reservoir_push': (rc, [vp, i32, traj, vp, u32, vp]),
+        'cs_reservoir_size': (rc, [vp, vp, vp]),
+        'cs_reservoir_gather': (rc, [vp, vp, i64, vp, vp, vp]),
+        'cs_reservoir_clear': (rc, [vp, vp]),
+        'cs_get_env_state': (rc, [vp, i64, vp, i32]),
+        'cs_copy_env_state': (rc, [vp, i64, vp, vp]),
+        'cs_set_step_record': (rc, [vp, i64, vp, vp]),
+        'cs_set_env_state': (rc, [vp, i64, vp, i32]),
+        'cs_env_rng_words': (rc, [vp, vp]),
+        'cs_copy_env_rng': (rc, [vp, i64, vp, vp]),
+        'cs_load_env_rng': (rc, [vp, i64, vp, vp]),
+        'cs_get_rng_ctl': (rc, [vp, i64, vp]),
+        'cs_debug_holdem_rank7': (rc, [vp, i64, vp, vp]),
+        'cs_debug_ddz_legal': (rc, [vp, vp, vp, i64, vp, vp]),
+        'cs_debug_set_serial_refill': (rc, [vp, i32]),
+        'cs_debug_set_kernel_flags': (rc, [vp, i32]),
+        'cs_last_error': (C.c_char_p, []),
+        'cs_version': (C.c_char_p, []),
+        'cs_abi_version': (i32, []),
+    }
+
+
+# every symbol include/cardsim.h declares: name -> (restype, argtypes). Tests check the library exports all of them; a
+# library that lacks one (an older A/B build loaded with CARDSIM_LIB) still loads, and call() raises where it is used
+PROTOTYPES = _prototypes()
+SYMBOLS = tuple(PROTOTYPES)
 
 POLICY_RANDOM, POLICY_RULE_V1, POLICY_RULE_V2 = 0, 1, 2   # CS_POLICY_* (rlcard_amd.models gives them names)
 
@@ -100,91 +153,20 @@ def lib():
         raise CardsimError('HIP engine not built: %s is missing (run __graft_entry__.build() or '
                            'make -C rlcard_amd/csrc)' % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
-    L.cs_game_info_get.argtypes = [i32, C.POINTER(Config), C.POINTER(GameInfo)]
-    L.cs_create.argtypes = [C.POINTER(vp), i32, i64, i32, C.POINTER(Config)]
-    L.cs_destroy.argtypes = [vp]
-    L.cs_destroy.restype = None
-    L.cs_seed.argtypes = [vp, vp, vp, i64, i64, vp]
-    L.cs_reset.argtypes = [vp, C.POINTER(StepOut), vp]
-    L.cs_step.argtypes = [vp, vp, C.POINTER(StepOut), vp]
-    L.cs_observe.argtypes = [vp, i32, C.POINTER(StepOut), vp]
-    L.cs_rollout.argtypes = [vp, i32, u64, u64, u64, C.POINTER(TrajOut), vp]
-    if hasattr(L, 'cs_traj_probe'):   # (older A/B builds lack it)
-        L.cs_traj_probe.argtypes = [vp, i32, C.POINTER(TrajOut), vp]
-    if hasattr(L, 'cs_state_bytes'):  # (ABI version 3)
-        L.cs_state_bytes.argtypes = [vp, vp]
-        L.cs_state_save.argtypes = [vp, vp, vp]
-        L.cs_state_load.argtypes = [vp, vp, vp]
-    if hasattr(L, 'cs_rollout_policy'):   # (added without an ABI version change: found by symbol)
-        L.cs_rollout_policy.argtypes = [vp, i32, u64, u64, u64, vp, C.POINTER(TrajOut), vp]
-        L.cs_policy_actions.argtypes = [vp, i32, u64, u64, u64, vp, vp]
-        L.cs_payoff_sums.argtypes = [vp, i32, C.POINTER(TrajOut), i32, vp, vp, vp, vp]
-    if hasattr(L, 'cs_qnet_actions'):   # (the DQN entry points, added the same way)
-        f32 = C.c_float
-        L.cs_qnet_values.argtypes = [vp, C.POINTER(QNet), vp, vp, i64, vp, vp]
-        L.cs_qnet_actions.argtypes = [vp, C.POINTER(QNet), vp, vp, vp, i64, f32, u64, u64, u64, vp, vp, vp]
-        L.cs_replay_create.argtypes = [vp, i64, C.POINTER(vp)]
-        L.cs_replay_destroy.argtypes = [vp]
-        L.cs_replay_destroy.restype = None
-        L.cs_replay_push.argtypes = [vp, i32, C.POINTER(TrajOut), C.c_uint32, vp]
-        L.cs_replay_drop_pending.argtypes = [vp, vp]
-        L.cs_replay_size.argtypes = [vp, vp, vp]
-        L.cs_replay_gather.argtypes = [vp, vp, i64, C.POINTER(ReplayBatch), vp]
-        L.cs_dqn_targets.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp]
-    if hasattr(L, 'cs_nfsp_actions'):   # (the NFSP entry points, added the same way)
-        f32 = C.c_float
-        L.cs_pnet_probs.argtypes = [vp, C.POINTER(QNet), vp, vp, i64, vp, vp]
-        L.cs_nfsp_scratch_bytes.argtypes = [i64]
-        L.cs_nfsp_scratch_bytes.restype = i64
-        L.cs_nfsp_actions.argtypes = [vp, C.POINTER(QNet), C.POINTER(QNet), vp, vp, vp, vp, i64, f32, u64, u64, u64, vp,
-                                      vp, vp, vp]
-        L.cs_reservoir_create.argtypes = [vp, i64, u64, C.POINTER(vp)]
-        L.cs_reservoir_destroy.argtypes = [vp]
-        L.cs_reservoir_destroy.restype = None
-        L.cs_reservoir_push.argtypes = [vp, i32, C.POINTER(TrajOut), vp, C.c_uint32, vp]
-        L.cs_reservoir_size.argtypes = [vp, vp, vp]
-        L.cs_reservoir_gather.argtypes = [vp, vp, i64, vp, vp, vp]
-        L.cs_reservoir_clear.argtypes = [vp, vp]
-    L.cs_transitions.argtypes = [vp, i32, C.POINTER(TrajOut), C.POINTER(TransOut), vp]
-    L.cs_legal_lists.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    L.cs_action_features.argtypes = [vp, vp, i64, vp, vp]
-    L.cs_get_env_state.argtypes = [vp, i64, vp, i32]
-    L.cs_set_env_state.argtypes = [vp, i64, vp, i32]
-    L.cs_copy_env_state.argtypes = [vp, i64, vp, vp]
-    L.cs_set_step_record.argtypes = [vp, i64, vp, vp]
-    L.cs_env_rng_words.argtypes = [vp, vp]
-    L.cs_copy_env_rng.argtypes = [vp, i64, vp, vp]
-    L.cs_load_env_rng.argtypes = [vp, i64, vp, vp]
-    L.cs_get_rng_ctl.argtypes = [vp, i64, vp]
-    L.cs_cfr_train.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
-    L.cs_debug_holdem_rank7.argtypes = [vp, i64, vp, vp]
-    L.cs_debug_ddz_legal.argtypes = [vp, vp, vp, i64, vp, vp]
-    L.cs_debug_set_serial_refill.argtypes = [vp, i32]
-    L.cs_debug_set_kernel_flags.argtypes = [vp, i32]
-    L.cs_dmc_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
-    L.cs_dmc_destroy.argtypes = [vp]
-    L.cs_dmc_destroy.restype = None
-    L.cs_dmc_fill.argtypes = [vp, i32, C.POINTER(TrajOut), vp, i64, vp, vp]
-    L.cs_dmc_gather.argtypes = [vp, i32, vp, i64, C.POINTER(DmcBatch), vp]
-    L.cs_dmc_status.argtypes = [vp, vp]
-    L.cs_dmc_layer1.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]
-    L.cs_dmc_select.argtypes = [vp, vp, vp, vp, i64, C.c_float, u64, u64, u64, vp, vp]
-    L.cs_last_error.restype = C.c_char_p
-    L.cs_version.restype = C.c_char_p
-    if hasattr(L, 'cs_abi_version'):   # (older A/B builds lack it)
-        L.cs_abi_version.restype = C.c_int32
-        if L.cs_abi_version() < ABI_VERSION:
-            raise CardsimError('%s implements ABI version %d, this binding needs %d' % (LIB_PATH, L.cs_abi_version(),
-                                                                                     ABI_VERSION))
-    for name in SYMBOLS:
-        if name not in ('cs_destroy', 'cs_dmc_destroy', 'cs_replay_destroy', 'cs_reservoir_destroy',
-                        'cs_nfsp_scratch_bytes', 'cs_last_error', 'cs_version', 'cs_abi_version'):
-            if name in OPTIONAL and not hasattr(L, name):   # older A/B builds (CARDSIM_LIB) lack it
-                continue
-            getattr(L, name).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
+    if has('cs_abi_version', L) and L.cs_abi_version() < ABI_VERSION:
+        raise CardsimError('%s implements ABI version %d, this binding needs %d' % (LIB_PATH, L.cs_abi_version(),
+                                                                                 ABI_VERSION))
     _lib = L
     return L
+
+
+def has(name, L=None):
+    """whether the loaded library exports `name`"""
+    return getattr(L or lib(), name, None) is not None
 
 
 def check(code, what=''):
@@ -193,10 +175,64 @@ def check(code, what=''):
         raise CardsimError('%s failed (%s): %s' % (what, _ERRORS.get(code, code), msg))
 
 
+def call(name, *args, device=None):
+    """The ABI function `name` on `args`, with `device` (when given) as torch's current device around it. A missing
+    symbol is an error, never a host fallback, and so is a negative return (CS_E_*); -> what the function returned."""
+    f = getattr(_lib or lib(), name, None)
+    if f is None:
+        raise CardsimError('%s lacks %s' % (LIB_PATH, name))
+    if device is None:
+        code = f(*args)
+    else:
+        with torch.cuda.device(device):
+            code = f(*args)
+    if code and code < 0:
+        check(code, name)
+    return code
+
+
+def ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """torch's current stream on `device`, as the ABI's `void* stream`"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def traj(tr, *keys):
+    """cs_traj_out of the trajectory dict `tr`: the tensors `keys` (each must be there), or every one it holds; NULL
+    elsewhere."""
+    if keys:
+        return TrajOut(**{k: ptr(tr[k]) for k in keys})
+    return TrajOut(*(ptr(tr.get(k)) for k, _ in TrajOut._fields_))
+
+
+class Handle:
+    """Owner of one object of the ABI: create() keeps the pointer a cs_*create call gives in _h, close() (and __del__)
+    hands it to the matching cs_*destroy once."""
+    _h = None
+
+    def create(self, name, *args, device=None, out_first=False):
+        h = C.c_void_p()
+        call(name, *((C.byref(h),) + args if out_first else args + (C.byref(h),)), device=device)
+        self._h, self._destroy = h, name.replace('create', 'destroy')
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            call(self._destroy, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def game_info(game, num_players=0, num_decks=-1, chips_for_each=0, dealer_id=None, rng_mode='mt19937'):
     cfg = Config(num_players, num_decks, chips_for_each, 0 if dealer_id is None else int(dealer_id) + 1,
                  RNG_MODES[rng_mode])
     info = GameInfo()
-    check(lib().cs_game_info_get(GAME_IDS[game] if isinstance(game, str) else game, C.byref(cfg), C.byref(info)),
-          'cs_game_info_get')
+    call('cs_game_info_get', GAME_IDS[game] if isinstance(game, str) else game, C.byref(cfg), C.byref(info))
     return info, cfg

@@ -9,7 +9,6 @@ With an rlcard_amd.make('leduc-holdem', {'allow_step_back': True, 'seed': s}) en
 stream exactly as the reference's env.reset() calls do, so the tables are bit-exact against the reference agent.
 With a VecEnv of B envs, every iteration deals B games per player (batched chance sampling).
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -71,18 +70,12 @@ class CFRAgent(object):
     def train(self, iterations=1):
         """`iterations` x the reference's train() (cfr_agent.py:30-43), on the device."""
         v = self._vecenv
-        with torch.cuda.device(v.device):
-            _abi.check(_abi.lib().cs_cfr_train(v._h, int(iterations), int(self.iteration), self._ptr(self._policy),
-                                               self._ptr(self._avg), self._ptr(self._regrets),
-                                               self._ptr(self._flags), v._stream()), 'cs_cfr_train')
+        _abi.call('cs_cfr_train', v._h, int(iterations), int(self.iteration), _abi.ptr(self._policy),
+                  _abi.ptr(self._avg), _abi.ptr(self._regrets), _abi.ptr(self._flags), v._stream(), device=v.device)
         self.iteration += int(iterations)
         self._host = None
         if isinstance(self.env, Env):   # the env holds the last deal at its root (every step was stepped back)
             self.env._sync_from_engine()
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr())
 
     # -- the reference's dicts ------------------------------------------------------------------------------------
     def _tables(self):

@@ -18,10 +18,7 @@ import torch
 from torch import nn
 
 from .. import _abi
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from .._abi import ptr as _ptr
 
 
 class DMCNet(nn.Module):
@@ -137,41 +134,25 @@ def shapes_of(vec):
     return [[vec.obs_dim]] * vec.num_players, [[vec.num_actions]] * vec.num_players
 
 
-class ActorBuffers:
+class ActorBuffers(_abi.Handle):
     """utils.py:49-163 for every env of `vec`: T-row chunks per (env, player) in an HBM ring of `slots` chunks."""
 
     def __init__(self, vec, T=100, slots=4):
         self.vec, self.T, self.slots = vec, int(T), int(slots)
         self.state_shape, _ = shapes_of(vec)
-        h = C.c_void_p()
-        with torch.cuda.device(vec.device):
-            _abi.check(_abi.lib().cs_dmc_create(vec._h, self.T, self.slots, C.byref(h)), 'cs_dmc_create')
-        self._d = h
+        self.create('cs_dmc_create', vec._h, self.T, self.slots, device=vec.device)
         self.feature_dim = vec.info.action_feature_dim
         self.cap = vec.num_envs * vec.num_players * self.slots
         self._ready = torch.empty(self.cap, dtype=torch.int64, device=vec.device)
         self._nready = torch.zeros(1, dtype=torch.int64, device=vec.device)
 
-    def close(self):
-        if getattr(self, '_d', None) is not None and self._d.value:
-            _abi.lib().cs_dmc_destroy(self._d)
-            self._d = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def fill(self, traj):
         """Append a trajectory ([T_roll][N] rows: obs, player, action, reward, done) -> the chunk ids that became
         ready (int64 tensor), in (env, player, chunk) order."""
         T = traj['player'].shape[0]
-        s = _abi.TrajOut(_ptr(traj['obs']), None, _ptr(traj['player']), _ptr(traj['action']), _ptr(traj['reward']),
-                         _ptr(traj['done']), None)
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_dmc_fill(self._d, int(T), C.byref(s), _ptr(self._ready), self.cap,
-                                              _ptr(self._nready), self.vec._stream()), 'cs_dmc_fill')
+        s = _abi.traj(traj, 'obs', 'player', 'action', 'reward', 'done')
+        _abi.call('cs_dmc_fill', self._h, int(T), C.byref(s), _ptr(self._ready), self.cap, _ptr(self._nready),
+                  self.vec._stream(), device=self.vec.device)
         n = int(self._nready.item())
         if self.dropped():
             raise _abi.CardsimError('DMC actor buffers overflowed: a (env, player) ring of %d chunks was full, rows were '
@@ -194,14 +175,13 @@ class ActorBuffers:
             ch = chunks.to(device=d, dtype=torch.int64).contiguous()
             b = _abi.DmcBatch(_ptr(out['state']), _ptr(out['action']), _ptr(out['target']), _ptr(out['done']),
                               _ptr(out['episode_return']))
-            with torch.cuda.device(d):
-                _abi.check(_abi.lib().cs_dmc_gather(self._d, int(player), _ptr(ch), B, C.byref(b),
-                                                    self.vec._stream()), 'cs_dmc_gather')
+            _abi.call('cs_dmc_gather', self._h, int(player), _ptr(ch), B, C.byref(b), self.vec._stream(),
+                      device=d)
         return out
 
     def dropped(self):
         v = C.c_uint32()
-        _abi.check(_abi.lib().cs_dmc_status(self._d, C.byref(v)), 'cs_dmc_status')
+        _abi.call('cs_dmc_status', self._h, C.byref(v))
         return bool(v.value & 1)
 
 
@@ -222,11 +202,8 @@ def _q_values(vec, net, obs, state_of, ids):
     E = int(ids.numel())
     h = torch.empty((E, H), dtype=torch.float32, device=obs.device)
     if E:
-        with torch.cuda.device(obs.device):
-            _abi.check(_abi.lib().cs_dmc_layer1(vec._h, _ptr(X.contiguous()), _ptr(state_of), _ptr(ids), E, H,
-                                                _ptr(Wa), _ptr(b1.contiguous()), _ptr(h),
-                                                C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)),
-                       'cs_dmc_layer1')
+        _abi.call('cs_dmc_layer1', vec._h, _ptr(X.contiguous()), _ptr(state_of), _ptr(ids), E, H, _ptr(Wa),
+                  _ptr(b1.contiguous()), _ptr(h), _abi.stream(obs.device), device=obs.device)
     for m in list(net.fc_layers)[2:]:
         h = m(h)
     return h.flatten()
@@ -237,11 +214,9 @@ def select_actions(values, counts, offsets, ids, eps=0.0, seed=0, t=0, state_bas
     S = int(counts.numel())
     out = torch.empty(S, dtype=torch.int32, device=values.device)
     if S:
-        with torch.cuda.device(values.device):
-            _abi.check(_abi.lib().cs_dmc_select(_ptr(values.contiguous()), _ptr(counts), _ptr(offsets), _ptr(ids), S,
-                                                float(eps), int(seed) & (2 ** 64 - 1), int(t), int(state_base),
-                                                _ptr(out), C.c_void_p(torch.cuda.current_stream(values.device)
-                                                                      .cuda_stream)), 'cs_dmc_select')
+        _abi.call('cs_dmc_select', _ptr(values.contiguous()), _ptr(counts), _ptr(offsets), _ptr(ids), S, float(eps),
+                  int(seed) & (2 ** 64 - 1), int(t), int(state_base), _ptr(out), _abi.stream(values.device),
+                  device=values.device)
     return out
 
 

@@ -22,14 +22,7 @@ import torch
 from torch import nn
 
 from .. import _abi
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from .._abi import ptr as _ptr
 
 
 def descriptor(wb, device):
@@ -209,53 +202,61 @@ def seat_mask(seats):
     return m
 
 
-class DeviceMemory:
+class DeviceBuffer(_abi.Handle):
+    """What the buffers of a VecEnv's envs in HBM share (DeviceMemory, nfsp_agent.DeviceReservoir): the two counters
+    of cs_<KIND>_size, the index tensor of gather() and sampling without replacement."""
+    KIND = None          # 'replay' / 'reservoir'
+    TOO_MANY = None      # sample()'s ValueError text for (asked, held)
+
+    def _call(self, what, *args):
+        """cs_<KIND>_<what>(buffer, *args) with the env's device current"""
+        return _abi.call('cs_%s_%s' % (self.KIND, what), self._h, *args, device=self.vec.device)
+
+    def sizes(self):
+        """(elements held, elements ever appended or offered); synchronises."""
+        size, total = C.c_int64(), C.c_int64()
+        self._call('size', C.byref(size), C.byref(total))
+        return size.value, total.value
+
+    def __len__(self):
+        return self.sizes()[0]
+
+    def _indices(self, idx):
+        """gather's idx as a flat int64 tensor on the env's device, and its length"""
+        idx = torch.as_tensor(idx, device=self.vec.device).to(torch.int64).contiguous().reshape(-1)
+        return idx, int(idx.numel())
+
+    def sample(self, count, generator=None):
+        """count distinct elements, uniformly (what random.sample gives the host buffers' sample), drawn from a
+        torch.Generator (None: torch's global one)."""
+        size = len(self)
+        if count > size:
+            raise ValueError(self.TOO_MANY % (count, size))
+        dev = generator.device if generator is not None else 'cpu'
+        return self.gather(torch.randperm(size, generator=generator, device=dev)[:count])
+
+
+class DeviceMemory(DeviceBuffer):
     """The replay memory of a VecEnv's envs in HBM (include/cardsim.h cs_replay): push() turns a rollout-layout
     trajectory into transitions on the device, in the FIFO order the header documents; index k is the k-th oldest
     transition held, as in Memory's list."""
+    KIND, TOO_MANY = 'replay', 'sample larger than the memory: %d > %d'
 
     def __init__(self, vec, capacity):
         self.vec, self.capacity = vec, int(capacity)
-        h = C.c_void_p()
-        with torch.cuda.device(vec.device):
-            _abi.check(_abi.lib().cs_replay_create(vec._h, self.capacity, C.byref(h)), 'cs_replay_create')
-        self._r = h
-
-    def close(self):
-        if getattr(self, '_r', None) is not None and self._r.value:
-            _abi.lib().cs_replay_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.create('cs_replay_create', vec._h, self.capacity, device=vec.device)
 
     def push(self, traj, seats):
         """Append the transitions of the seats `seats` of a trajectory ([T][N] rows with final_obs: VecEnv.rollout(...,
         final_obs=True) or DQNCollector's)."""
         T = traj['player'].shape[0]
-        s = _abi.TrajOut(*(_ptr(traj[k]) for k in ('obs', 'legal', 'player', 'action', 'reward', 'done', 'final_obs')))
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_replay_push(self._r, int(T), C.byref(s), seat_mask(seats), self.vec._stream()),
-                       'cs_replay_push')
+        s = _abi.traj(traj, 'obs', 'legal', 'player', 'action', 'reward', 'done', 'final_obs')
+        self._call('push', int(T), C.byref(s), seat_mask(seats), self.vec._stream())
 
     def drop_pending(self):
         """Forget the transitions waiting for their next state (after vec.reset() or a re-seed: their games are
         gone)."""
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_replay_drop_pending(self._r, self.vec._stream()), 'cs_replay_drop_pending')
-
-    def sizes(self):
-        """(transitions held, transitions ever appended); synchronises."""
-        size, total = C.c_int64(), C.c_int64()
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_replay_size(self._r, C.byref(size), C.byref(total)), 'cs_replay_size')
-        return size.value, total.value
-
-    def __len__(self):
-        return self.sizes()[0]
+        self._call('drop_pending', self.vec._stream())
 
     @property
     def total(self):
@@ -265,8 +266,7 @@ class DeviceMemory:
         """Transitions idx (int64, each in [0, len(self))) -> dict of device tensors: state / next_state float32
         [B, obs_dim], action int64 [B], reward float32 [B], next_legal uint8 [B, legal_bytes], done uint8 [B]."""
         v, d = self.vec, self.vec.device
-        idx = torch.as_tensor(idx, device=d).to(torch.int64).contiguous().reshape(-1)
-        B = int(idx.numel())
+        idx, B = self._indices(idx)
         out = dict(state=torch.empty((B, v.obs_dim), dtype=torch.float32, device=d),
                    action=torch.empty(B, dtype=torch.int64, device=d),
                    reward=torch.empty(B, dtype=torch.float32, device=d),
@@ -276,19 +276,8 @@ class DeviceMemory:
         if B:
             b = _abi.ReplayBatch(*(_ptr(out[k]) for k in ('state', 'action', 'reward', 'next_state', 'next_legal',
                                                           'done')))
-            with torch.cuda.device(d):
-                _abi.check(_abi.lib().cs_replay_gather(self._r, _ptr(idx), B, C.byref(b), v._stream()),
-                           'cs_replay_gather')
+            self._call('gather', _ptr(idx), B, C.byref(b), v._stream())
         return out
-
-    def sample(self, batch_size, generator=None):
-        """batch_size distinct transitions, uniformly (what random.sample gives Memory.sample), drawn from a
-        torch.Generator (None: torch's global one)."""
-        size = len(self)
-        if batch_size > size:
-            raise ValueError('sample larger than the memory: %d > %d' % (batch_size, size))
-        dev = generator.device if generator is not None else 'cpu'
-        return self.gather(torch.randperm(size, generator=generator, device=dev)[:batch_size])
 
 
 def dqn_targets(q_next, q_next_target, next_legal, reward, done, gamma):
@@ -298,11 +287,9 @@ def dqn_targets(q_next, q_next_target, next_legal, reward, done, gamma):
     target = torch.empty(B, dtype=torch.float32, device=d)
     best = torch.empty(B, dtype=torch.int32, device=d)
     if B:
-        with torch.cuda.device(d):
-            _abi.check(_abi.lib().cs_dqn_targets(_ptr(q_next.contiguous()), _ptr(q_next_target.contiguous()),
-                                                 _ptr(next_legal.contiguous()), _ptr(reward.contiguous()),
-                                                 _ptr(done.contiguous()), B, A, float(gamma), _ptr(target),
-                                                 _ptr(best), _stream(d)), 'cs_dqn_targets')
+        _abi.call('cs_dqn_targets', _ptr(q_next.contiguous()), _ptr(q_next_target.contiguous()),
+                  _ptr(next_legal.contiguous()), _ptr(reward.contiguous()), _ptr(done.contiguous()), B, A, float(gamma),
+                  _ptr(target), _ptr(best), _abi.stream(d), device=d)
     return target, best
 
 
@@ -441,10 +428,8 @@ class DQNAgent:
         obs, legal, done = state['obs'], state['legal'], state.get('done')
         rows = obs.shape[0]
         out = torch.empty(rows, dtype=torch.int32, device=v.device)
-        with torch.cuda.device(v.device):
-            _abi.check(_abi.lib().cs_qnet_actions(v._h, C.byref(net), _ptr(obs), _ptr(legal), _ptr(done), rows,
-                                                  float(eps), int(seed) & (2 ** 64 - 1), int(t), v.env_base, _ptr(out),
-                                                  _ptr(q), v._stream()), 'cs_qnet_actions')
+        _abi.call('cs_qnet_actions', v._h, C.byref(net), _ptr(obs), _ptr(legal), _ptr(done), rows, float(eps),
+                  int(seed) & (2 ** 64 - 1), int(t), v.env_base, _ptr(out), _ptr(q), v._stream(), device=v.device)
         return out
 
     def step_vec(self, state, t, seed=0):
@@ -462,9 +447,8 @@ class DQNAgent:
         v = self.vec
         net = self.q_estimator.folded()
         q = torch.empty((obs.shape[0], self.num_actions), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _abi.check(_abi.lib().cs_qnet_values(v._h, C.byref(net), _ptr(obs), _ptr(legal), obs.shape[0], _ptr(q),
-                                                 v._stream()), 'cs_qnet_values')
+        _abi.call('cs_qnet_values', v._h, C.byref(net), _ptr(obs), _ptr(legal), obs.shape[0], _ptr(q), v._stream(),
+                  device=v.device)
         return q
 
     def train_steps_for(self, t0, t1):

@@ -24,7 +24,8 @@ from torch import nn
 
 from .. import _abi
 from ..utils import remove_illegal
-from .dqn_agent import DQNAgent, DQNCollector, _ptr, descriptor, fold_batchnorm, seat_mask
+from .._abi import ptr as _ptr
+from .dqn_agent import DQNAgent, DQNCollector, DeviceBuffer, descriptor, fold_batchnorm, seat_mask
 
 Transition = namedtuple('Transition', 'info_state action_probs')
 
@@ -134,29 +135,16 @@ class ReservoirBuffer:
         return iter(self._data)
 
 
-class DeviceReservoir:
+class DeviceReservoir(DeviceBuffer):
     """The reservoir buffer of a VecEnv's envs in HBM (include/cardsim.h cs_reservoir): push() offers a rollout-layout
     trajectory's best-response rows with ReservoirBuffer.add's semantics, the replacement draws Philox keyed by `seed`
-    on the element's stream index; index k is slot k, as in ReservoirBuffer's list."""
+    on the element's stream index; index k is slot k, as in ReservoirBuffer's list. sizes(): (elements held, elements
+    ever offered: ReservoirBuffer._add_calls)."""
+    KIND, TOO_MANY = 'reservoir', '%d elements could not be sampled from size %d'
 
     def __init__(self, vec, capacity, seed=0):
         self.vec, self.capacity, self.seed = vec, int(capacity), int(seed) & (2 ** 64 - 1)
-        h = C.c_void_p()
-        with torch.cuda.device(vec.device):
-            _abi.check(_abi.lib().cs_reservoir_create(vec._h, self.capacity, self.seed, C.byref(h)),
-                       'cs_reservoir_create')
-        self._r = h
-
-    def close(self):
-        if getattr(self, '_r', None) is not None and self._r.value:
-            _abi.lib().cs_reservoir_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.create('cs_reservoir_create', vec._h, self.capacity, self.seed, device=vec.device)
 
     def push(self, traj, mode_rows, seats):
         """Offer the rows of a trajectory ([T][N] rows) that the seats `seats` played with mode_rows[t][e] != 0 (uint8
@@ -164,21 +152,8 @@ class DeviceReservoir:
         T = traj['player'].shape[0]
         if tuple(mode_rows.shape) != tuple(traj['player'].shape) or mode_rows.dtype != torch.uint8:
             raise ValueError('mode_rows must be uint8 %s' % (tuple(traj['player'].shape),))
-        s = _abi.TrajOut(*(_ptr(traj.get(k)) for k in ('obs', 'legal', 'player', 'action', 'reward', 'done',
-                                                       'final_obs')))
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_reservoir_push(self._r, int(T), C.byref(s), _ptr(mode_rows.contiguous()),
-                                                    seat_mask(seats), self.vec._stream()), 'cs_reservoir_push')
-
-    def sizes(self):
-        """(elements held, elements ever offered: ReservoirBuffer._add_calls); synchronises."""
-        size, calls = C.c_int64(), C.c_int64()
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_reservoir_size(self._r, C.byref(size), C.byref(calls)), 'cs_reservoir_size')
-        return size.value, calls.value
-
-    def __len__(self):
-        return self.sizes()[0]
+        self._call('push', int(T), C.byref(_abi.traj(traj)), _ptr(mode_rows.contiguous()), seat_mask(seats),
+                   self.vec._stream())
 
     @property
     def add_calls(self):
@@ -188,29 +163,15 @@ class DeviceReservoir:
         """Slots idx (int64, each in [0, len(self))) -> dict of device tensors: state float32 [B, obs_dim],
         action_probs float32 [B, num_actions] (one-hot)."""
         v, d = self.vec, self.vec.device
-        idx = torch.as_tensor(idx, device=d).to(torch.int64).contiguous().reshape(-1)
-        B = int(idx.numel())
+        idx, B = self._indices(idx)
         out = dict(state=torch.empty((B, v.obs_dim), dtype=torch.float32, device=d),
                    action_probs=torch.empty((B, v.num_actions), dtype=torch.float32, device=d))
         if B:
-            with torch.cuda.device(d):
-                _abi.check(_abi.lib().cs_reservoir_gather(self._r, _ptr(idx), B, _ptr(out['state']),
-                                                          _ptr(out['action_probs']), v._stream()),
-                           'cs_reservoir_gather')
+            self._call('gather', _ptr(idx), B, _ptr(out['state']), _ptr(out['action_probs']), v._stream())
         return out
 
-    def sample(self, num_samples, generator=None):
-        """num_samples distinct elements, uniformly (what random.sample gives ReservoirBuffer.sample), drawn from a
-        torch.Generator (None: torch's global one)."""
-        size = len(self)
-        if num_samples > size:
-            raise ValueError('{} elements could not be sampled from size {}'.format(num_samples, size))
-        dev = generator.device if generator is not None else 'cpu'
-        return self.gather(torch.randperm(size, generator=generator, device=dev)[:num_samples])
-
     def clear(self):
-        with torch.cuda.device(self.vec.device):
-            _abi.check(_abi.lib().cs_reservoir_clear(self._r, self.vec._stream()), 'cs_reservoir_clear')
+        self._call('clear', self.vec._stream())
 
 
 class NFSPAgent:
@@ -406,22 +367,17 @@ class NFSPAgent:
         v = self._need_vec()
         obs, legal, done = state['obs'], state['legal'], state.get('done')
         rows = obs.shape[0]
-        L = _abi.lib()
         out = torch.empty(rows, dtype=torch.int32, device=v.device)
         qnet = None
         if mode_rows is not None:
             qnet = C.byref(self._rl_agent.q_estimator.folded())
             if self._scratch is None or self._scratch[0] != rows:
-                need = L.cs_nfsp_scratch_bytes(rows)
-                if need < 0:
-                    _abi.check(int(need), 'cs_nfsp_scratch_bytes')
+                need = _abi.call('cs_nfsp_scratch_bytes', rows)
                 self._scratch = (rows, torch.empty(need, dtype=torch.uint8, device=v.device))
         scratch = self._scratch[1] if mode_rows is not None else None
-        with torch.cuda.device(v.device):
-            _abi.check(L.cs_nfsp_actions(v._h, qnet, C.byref(self.policy_network.folded()), _ptr(obs), _ptr(legal),
-                                         _ptr(done), _ptr(mode_rows), rows, float(eps), int(seed) & (2 ** 64 - 1),
-                                         int(t), v.env_base, _ptr(out), _ptr(probs), _ptr(scratch), v._stream()),
-                       'cs_nfsp_actions')
+        _abi.call('cs_nfsp_actions', v._h, qnet, C.byref(self.policy_network.folded()), _ptr(obs), _ptr(legal),
+                  _ptr(done), _ptr(mode_rows), rows, float(eps), int(seed) & (2 ** 64 - 1), int(t), v.env_base,
+                  _ptr(out), _ptr(probs), _ptr(scratch), v._stream(), device=v.device)
         return out
 
     def step_vec(self, state, t, seed=0, mode_rows=None):
@@ -446,9 +402,8 @@ class NFSPAgent:
         illegal."""
         v = self._need_vec()
         probs = torch.empty((obs.shape[0], self._num_actions), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _abi.check(_abi.lib().cs_pnet_probs(v._h, C.byref(self.policy_network.folded()), _ptr(obs), _ptr(legal),
-                                                obs.shape[0], _ptr(probs), v._stream()), 'cs_pnet_probs')
+        _abi.call('cs_pnet_probs', v._h, C.byref(self.policy_network.folded()), _ptr(obs), _ptr(legal), obs.shape[0],
+                  _ptr(probs), v._stream(), device=v.device)
         return probs
 
     def sl_steps_for(self, t0, t1):

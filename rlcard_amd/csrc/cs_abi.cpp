@@ -22,9 +22,18 @@ struct cs_handle {
     bool seeded;
     void* table_dev;     // doudizhu: device action table (one allocation)
     cs::ddz::Tab tab;    // doudizhu: views into it, passed to the kernels by value
-    void* scan_tmp;      // cs_legal_lists: prefix-scan scratch, grown on demand
-    size_t scan_bytes;
-    cs::CfrScratch cfr;  // cs_cfr_train with n > 1: the ordered reduction's records and sort buffers
+    cs::DevBuf scan;     // cs_legal_lists: prefix-scan scratch, grown on demand
+    cs::DevBuf cfr;      // cs_cfr_train with n > 1: the ordered reduction's records and sort buffers
+};
+
+// What the buffers created on a handle (cs_dmc, cs_replay, cs_reservoir) share. A buffer may outlive its handle only
+// to be destroyed: destroy uses `device`, never `h`.
+struct cs_sub {
+    cs_handle* h;
+    int32_t device;      // h->device, copied at create
+    cs::DevBuf mem;      // one allocation carved into the buffer's parts
+    cs::DevBuf scratch;  // per-call scratch sized by the call's window, grown on demand
+    cs::DevBuf scan;     // prefix-scan scratch, grown on demand
 };
 
 namespace {
@@ -42,10 +51,49 @@ int fail_hip(hipError_t e, const char* where)
     return CS_E_DEVICE;
 }
 
-int set_device(const cs_handle* h)
+int done(hipError_t e, const char* where) { return e == hipSuccess ? CS_OK : fail_hip(e, where); }
+
+int set_device(const cs_handle* h) { return done(hipSetDevice(h->device), "hipSetDevice"); }
+
+// cs_reset / cs_step / cs_observe under a step record: the call publishes the next sequence number, and a launch that
+// failed published nothing
+template <class Launch>
+int recorded(cs_handle* h, const char* name, Launch launch)
 {
-    hipError_t e = hipSetDevice(h->device);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "hipSetDevice");
+    if (h->b.rec.seq) h->b.rec.seqv++;
+    const hipError_t e = launch();
+    if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;
+    return done(e, name);
+}
+
+// A buffer of handle h: its one allocation of `total` bytes, zeroed from byte `zero_from` on
+template <class S>
+int sub_create(cs_handle* h, size_t total, size_t zero_from, const char* name, S** out)
+{
+    S* s = new (std::nothrow) S();
+    if (!s) return fail(CS_E_INVALID, "out of host memory");
+    s->h = h;
+    s->device = h->device;
+    hipError_t e = s->mem.reserve(total);
+    if (e == hipSuccess) e = hipMemset((uint8_t*)s->mem.p + zero_from, 0, total - zero_from);
+    if (e != hipSuccess) {
+        s->mem.release();
+        delete s;
+        return fail_hip(e, name);
+    }
+    *out = s;
+    return CS_OK;
+}
+
+template <class S>
+void sub_destroy(S* s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    s->mem.release();
+    s->scratch.release();
+    s->scan.release();
+    delete s;
 }
 
 // the device buffers that hold the envs' state (cs_state_*): pointer and bytes of each, in a fixed order
@@ -148,8 +196,8 @@ void cs_destroy(cs_handle* h)
     if (h->b.sctl) (void)hipFree(h->b.sctl);
     if (h->b.sbuf) (void)hipFree(h->b.sbuf);
     if (h->table_dev) (void)hipFree(h->table_dev);
-    if (h->scan_tmp) (void)hipFree(h->scan_tmp);
-    if (h->cfr.mem) (void)hipFree(h->cfr.mem);
+    h->scan.release();
+    h->cfr.release();
     delete h;
 }
 
@@ -190,10 +238,7 @@ int cs_reset(cs_handle* h, const cs_step_out* out, void* stream)
     if (!h->seeded) return fail(CS_E_STATE, "cs_reset before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = h->ops->reset(h->b, *out, (hipStream_t)stream);
-    if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reset");
+    return recorded(h, "cs_reset", [&] { return h->ops->reset(h->b, *out, (hipStream_t)stream); });
 }
 
 int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* stream)
@@ -202,10 +247,7 @@ int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* 
     if (!h->seeded) return fail(CS_E_STATE, "cs_step before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = h->ops->step(h->b, actions, *out, (hipStream_t)stream);
-    if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_step");
+    return recorded(h, "cs_step", [&] { return h->ops->step(h->b, actions, *out, (hipStream_t)stream); });
 }
 
 int cs_observe(cs_handle* h, int32_t player, const cs_step_out* out, void* stream)
@@ -214,10 +256,7 @@ int cs_observe(cs_handle* h, int32_t player, const cs_step_out* out, void* strea
     if (player < 0 || player >= h->ops->info.num_players) return fail(CS_E_INVALID, "player out of range");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    if (h->b.rec.seq) h->b.rec.seqv++;
-    hipError_t e = h->ops->observe(h->b, player, *out, (hipStream_t)stream);
-    if (e != hipSuccess && h->b.rec.seq) h->b.rec.seqv--;   // nothing published for this call
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_observe");
+    return recorded(h, "cs_observe", [&] { return h->ops->observe(h->b, player, *out, (hipStream_t)stream); });
 }
 
 int cs_set_step_record(cs_handle* h, int64_t env, uint32_t* words, uint32_t* seq)
@@ -240,8 +279,7 @@ int cs_cfr_train(cs_handle* h, int32_t iterations, int64_t iteration0, double* p
     int r = set_device(h);
     if (r != CS_OK) return r;
     const cs::CfrTables t{policy, average_policy, regrets, flags};
-    hipError_t e = cs::launch_cfr(h->b, iterations, iteration0, t, &h->cfr, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_cfr_train");
+    return done(cs::launch_cfr(h->b, iterations, iteration0, t, h->cfr, (hipStream_t)stream), "cs_cfr_train");
 }
 
 int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint64_t env_base, const cs_traj_out* out,
@@ -254,8 +292,7 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
     if (!h->seeded) return fail(CS_E_STATE, "cs_rollout before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = h->ops->rollout(h->b, T, policy_seed, t0, env_base, *out, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_rollout");
+    return done(h->ops->rollout(h->b, T, policy_seed, t0, env_base, *out, (hipStream_t)stream), "cs_rollout");
 }
 
 int cs_rollout_policy(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint64_t env_base,
@@ -287,7 +324,7 @@ int cs_rollout_policy(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0
         }
         e = h->ops->rollout_policy(h->b, T, policy_seed, t0, env_base, seats, *out, (hipStream_t)stream);
     }
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_rollout_policy");
+    return done(e, "cs_rollout_policy");
 }
 
 int cs_policy_actions(cs_handle* h, int32_t policy, uint64_t policy_seed, uint64_t t, uint64_t env_base,
@@ -300,8 +337,8 @@ int cs_policy_actions(cs_handle* h, int32_t policy, uint64_t policy_seed, uint64
     if (!h->seeded) return fail(CS_E_STATE, "cs_policy_actions before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = h->ops->policy_actions(h->b, policy, policy_seed, t, env_base, actions, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_policy_actions");
+    return done(h->ops->policy_actions(h->b, policy, policy_seed, t, env_base, actions, (hipStream_t)stream),
+                                       "cs_policy_actions");
 }
 
 int cs_payoff_sums(cs_handle* h, int32_t T, const cs_traj_out* traj, int32_t quota, int32_t* games_per_env,
@@ -312,19 +349,13 @@ int cs_payoff_sums(cs_handle* h, int32_t T, const cs_traj_out* traj, int32_t quo
     if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_payoff_sums(h->b, T, *traj, quota, games_per_env, sums, games, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_payoff_sums");
+    return done(cs::launch_payoff_sums(h->b, T, *traj, quota, games_per_env, sums, games, (hipStream_t)stream),
+                                       "cs_payoff_sums");
 }
 
 // ---- DMC ----------------------------------------------------------------------------------------------------------
-struct cs_dmc {
-    cs_handle* h;
+struct cs_dmc : cs_sub {   // mem: the ring and the counters; scratch: i64 [rows], the ring row of each trajectory row
     cs::DmcRing r;
-    void* mem;          // one allocation for the ring and the counters
-    int64_t* dst;       // [rows] ring row of each trajectory row (grown on demand)
-    int64_t dst_rows;
-    void* scan_tmp;
-    size_t scan_bytes;
 };
 
 int cs_dmc_create(cs_handle* h, int32_t T, int32_t slots, cs_dmc** out)
@@ -336,40 +367,24 @@ int cs_dmc_create(cs_handle* h, int32_t T, int32_t slots, cs_dmc** out)
     if (r != CS_OK) return r;
     const int64_t streams = h->b.n * h->ops->info.num_players, rows = streams * slots * (int64_t)T;
     const int64_t O = h->ops->info.obs_dim, F = h->ops->info.action_feature_dim;
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    const int64_t o_st = 0, o_act = o_st + al(rows * O), o_tgt = o_act + al(rows * F), o_ret = o_tgt + al(rows * 4),
-                  o_dne = o_ret + al(rows * 4), o_ctr = o_dne + al(rows), o_gs = o_ctr + al(streams * 8),
-                  o_em = o_gs + al(streams * 8), o_cnt = o_em + al(streams * 8), o_off = o_cnt + al((streams + 1) * 4),
-                  o_flag = o_off + al((streams + 1) * 8), total = o_flag + 256;
-    cs_dmc* d = new (std::nothrow) cs_dmc();
-    if (!d) return fail(CS_E_INVALID, "out of host memory");
-    hipError_t e = hipMalloc(&d->mem, (size_t)total);
-    if (e != hipSuccess) { delete d; return fail_hip(e, "cs_dmc_create"); }
-    uint8_t* m = (uint8_t*)d->mem;
+    cs::Carve c;
+    const size_t o_st = c.take<int8_t>(rows * O), o_act = c.take<int8_t>(rows * F), o_tgt = c.take<float>(rows),
+                 o_ret = c.take<float>(rows), o_dne = c.take<uint8_t>(rows), o_ctr = c.take<int64_t>(streams),
+                 o_gs = c.take<int64_t>(streams), o_em = c.take<int64_t>(streams),
+                 o_cnt = c.take<int32_t>(streams + 1), o_off = c.take<int64_t>(streams + 1),
+                 o_flag = c.take<uint32_t>(1);
     // counters, counts (incl. the trailing 0) and the flag start at zero; the ring rows are written before read
-    e = hipMemset(m + o_ctr, 0, (size_t)(total - o_ctr));
-    if (e != hipSuccess) { (void)hipFree(d->mem); delete d; return fail_hip(e, "cs_dmc_create"); }
-    d->h = h;
+    cs_dmc* d = nullptr;
+    if ((r = sub_create(h, c.bytes(), o_ctr, "cs_dmc_create", &d)) != CS_OK) return r;
+    uint8_t* m = (uint8_t*)d->mem.p;
     d->r = cs::DmcRing{T, slots, (int32_t)F, (int8_t*)(m + o_st), (int8_t*)(m + o_act), (float*)(m + o_tgt),
                        (float*)(m + o_ret), m + o_dne, (int64_t*)(m + o_ctr), (int64_t*)(m + o_gs),
                        (int64_t*)(m + o_em), (int32_t*)(m + o_cnt), (int64_t*)(m + o_off), (uint32_t*)(m + o_flag)};
-    d->dst = nullptr;
-    d->dst_rows = 0;
-    d->scan_tmp = nullptr;
-    d->scan_bytes = 0;
     *out = d;
     return CS_OK;
 }
 
-void cs_dmc_destroy(cs_dmc* d)
-{
-    if (!d) return;
-    (void)hipSetDevice(d->h->device);
-    if (d->mem) (void)hipFree(d->mem);
-    if (d->dst) (void)hipFree(d->dst);
-    if (d->scan_tmp) (void)hipFree(d->scan_tmp);
-    delete d;
-}
+void cs_dmc_destroy(cs_dmc* d) { sub_destroy(d); }
 
 int cs_dmc_fill(cs_dmc* d, int32_t T_roll, const cs_traj_out* traj, int64_t* ready, int64_t cap, int64_t* nready,
                 void* stream)
@@ -380,17 +395,11 @@ int cs_dmc_fill(cs_dmc* d, int32_t T_roll, const cs_traj_out* traj, int64_t* rea
     int r = set_device(d->h);
     if (r != CS_OK) return r;
     const int64_t rows = (int64_t)T_roll * d->h->b.n;
-    if (rows > d->dst_rows) {
-        if (d->dst) (void)hipFree(d->dst);
-        d->dst = nullptr;
-        d->dst_rows = 0;
-        hipError_t e = hipMalloc((void**)&d->dst, (size_t)rows * sizeof(int64_t));
-        if (e != hipSuccess) return fail_hip(e, "cs_dmc_fill");
-        d->dst_rows = rows;
-    }
-    hipError_t e = cs::launch_dmc_fill(d->h->b, d->r, T_roll, *traj, ready, cap, nready, d->dst, &d->scan_tmp,
-                                       &d->scan_bytes, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_fill");
+    hipError_t e = d->scratch.reserve((size_t)rows * sizeof(int64_t));
+    if (e == hipSuccess)
+        e = cs::launch_dmc_fill(d->h->b, d->r, T_roll, *traj, ready, cap, nready, (int64_t*)d->scratch.p, d->scan,
+                                (hipStream_t)stream);
+    return done(e, "cs_dmc_fill");
 }
 
 int cs_dmc_gather(cs_dmc* d, int32_t player, const int64_t* chunks, int64_t count, const cs_dmc_batch* out,
@@ -404,8 +413,7 @@ int cs_dmc_gather(cs_dmc* d, int32_t player, const int64_t* chunks, int64_t coun
     if (r != CS_OK) return r;
     const int32_t od = d->h->ops->info.obs_dim;
     const int32_t sd = d->h->b.game == CS_GAME_DOUDIZHU && player == 0 ? cs::ddz::OBS_LANDLORD : od;
-    hipError_t e = cs::launch_dmc_gather(d->r, sd, od, chunks, count, *out, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_gather");
+    return done(cs::launch_dmc_gather(d->r, sd, od, chunks, count, *out, (hipStream_t)stream), "cs_dmc_gather");
 }
 
 int cs_dmc_status(cs_dmc* d, uint32_t* host_flags)
@@ -413,8 +421,7 @@ int cs_dmc_status(cs_dmc* d, uint32_t* host_flags)
     if (!d || !host_flags) return fail(CS_E_INVALID, "null argument");
     int r = set_device(d->h);
     if (r != CS_OK) return r;
-    hipError_t e = hipMemcpy(host_flags, d->r.flag, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_status");
+    return done(hipMemcpy(host_flags, d->r.flag, sizeof(uint32_t), hipMemcpyDeviceToHost), "cs_dmc_status");
 }
 
 int cs_dmc_layer1(cs_handle* h, const float* X, const int32_t* state_of, const int32_t* ids, int64_t E, int32_t H,
@@ -425,9 +432,8 @@ int cs_dmc_layer1(cs_handle* h, const float* X, const int32_t* state_of, const i
     if (E == 0) return CS_OK;
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_dmc_layer1(X, state_of, ids, E, H, W_act, b1, h->ops->info.action_feature_dim, h->b, h1,
-                                         (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_layer1");
+    return done(cs::launch_dmc_layer1(X, state_of, ids, E, H, W_act, b1, h->ops->info.action_feature_dim, h->b, h1,
+                                      (hipStream_t)stream), "cs_dmc_layer1");
 }
 
 int cs_dmc_select(const float* values, const int32_t* counts, const int64_t* offsets, const int32_t* ids, int64_t S,
@@ -435,9 +441,8 @@ int cs_dmc_select(const float* values, const int32_t* counts, const int64_t* off
 {
     if (!values || !counts || !offsets || !ids || !actions) return fail(CS_E_INVALID, "null argument");
     if (S <= 0) return fail(CS_E_INVALID, "S must be positive");
-    hipError_t e = cs::launch_dmc_select(values, counts, offsets, ids, S, eps, seed, t, state_base, actions,
-                                         (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dmc_select");
+    return done(cs::launch_dmc_select(values, counts, offsets, ids, S, eps, seed, t, state_base, actions,
+                                      (hipStream_t)stream), "cs_dmc_select");
 }
 
 // ---- DQN ----------------------------------------------------------------------------------------------------------
@@ -469,9 +474,8 @@ int cs_qnet_values(cs_handle* h, const cs_qnet* net, const void* obs, const void
     if (!q) return fail(CS_E_INVALID, "null argument");
     if (rows == 0) return CS_OK;
     if ((r = set_device(h)) != CS_OK) return r;
-    hipError_t e = cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0.f, 0, 0, 0,
-                                   nullptr, q, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_qnet_values");
+    return done(cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0.f, 0, 0, 0, nullptr,
+                                q, (hipStream_t)stream), "cs_qnet_values");
 }
 
 int cs_qnet_actions(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, const void* done,
@@ -483,19 +487,12 @@ int cs_qnet_actions(cs_handle* h, const cs_qnet* net, const void* obs, const voi
     if (!actions) return fail(CS_E_INVALID, "null argument");
     if (rows == 0) return CS_OK;
     if ((r = set_device(h)) != CS_OK) return r;
-    hipError_t e = cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done, rows, eps,
-                                   seed, t, row_base, actions, q, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_qnet_actions");
+    return ::done(cs::launch_qnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done, rows, eps,
+                                  seed, t, row_base, actions, q, (hipStream_t)stream), "cs_qnet_actions");
 }
 
-struct cs_replay {
-    cs_handle* h;
-    cs::ReplayRing r;
-    void* mem;          // one allocation for the ring, the pending store and the counter
-    int32_t* scratch;   // code and pos of a push, [2][entries] (grown on demand)
-    int64_t entries;
-    void* scan_tmp;
-    size_t scan_bytes;
+struct cs_replay : cs_sub {   // mem: the ring, the pending store and the counter; scratch: i32 [2][entries], code and
+    cs::ReplayRing r;         // pos of a push
 };
 
 int cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out)
@@ -508,40 +505,23 @@ int cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out)
     int r = set_device(h);
     if (r != CS_OK) return r;
     const int64_t O = info.obs_dim, LB = info.legal_bytes, NP = h->b.n * info.num_players, cap = capacity;
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    const int64_t o_st = 0, o_nst = o_st + al(cap * O), o_nlg = o_nst + al(cap * O), o_act = o_nlg + al(cap * LB),
-                  o_rew = o_act + al(cap * 4), o_dne = o_rew + al(cap * 4), o_pst = o_dne + al(cap),
-                  o_pact = o_pst + al(NP * O), o_np = o_pact + al(NP * 4), o_pv = o_np + al(NP * 4),
-                  o_tot = o_pv + al(NP), total = o_tot + 256;
-    cs_replay* p = new (std::nothrow) cs_replay();
-    if (!p) return fail(CS_E_INVALID, "out of host memory");
-    hipError_t e = hipMalloc(&p->mem, (size_t)total);
-    if (e != hipSuccess) { delete p; return fail_hip(e, "cs_replay_create"); }
-    uint8_t* m = (uint8_t*)p->mem;
+    cs::Carve c;
+    const size_t o_st = c.take<uint8_t>(cap * O), o_nst = c.take<uint8_t>(cap * O), o_nlg = c.take<uint8_t>(cap * LB),
+                 o_act = c.take<int32_t>(cap), o_rew = c.take<float>(cap), o_dne = c.take<uint8_t>(cap),
+                 o_pst = c.take<uint8_t>(NP * O), o_pact = c.take<int32_t>(NP), o_np = c.take<int32_t>(NP),
+                 o_pv = c.take<uint8_t>(NP), o_tot = c.take<int64_t>(1);
     // no pending rows, nothing appended; the slots are written before they are read
-    e = hipMemset(m + o_pv, 0, (size_t)(total - o_pv));
-    if (e != hipSuccess) { (void)hipFree(p->mem); delete p; return fail_hip(e, "cs_replay_create"); }
-    p->h = h;
+    cs_replay* p = nullptr;
+    if ((r = sub_create(h, c.bytes(), o_pv, "cs_replay_create", &p)) != CS_OK) return r;
+    uint8_t* m = (uint8_t*)p->mem.p;
     p->r = cs::ReplayRing{cap, (int32_t)O, (int32_t)LB, info.num_players, info.action_bytes, m + o_st, m + o_nst,
                           m + o_nlg, (int32_t*)(m + o_act), (float*)(m + o_rew), m + o_dne, (int64_t*)(m + o_tot),
                           m + o_pv, m + o_pst, (int32_t*)(m + o_pact), (int32_t*)(m + o_np)};
-    p->scratch = nullptr;
-    p->entries = 0;
-    p->scan_tmp = nullptr;
-    p->scan_bytes = 0;
     *out = p;
     return CS_OK;
 }
 
-void cs_replay_destroy(cs_replay* r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->h->device);
-    if (r->mem) (void)hipFree(r->mem);
-    if (r->scratch) (void)hipFree(r->scratch);
-    if (r->scan_tmp) (void)hipFree(r->scan_tmp);
-    delete r;
-}
+void cs_replay_destroy(cs_replay* r) { sub_destroy(r); }
 
 int cs_replay_push(cs_replay* r, int32_t T, const cs_traj_out* traj, uint32_t seat_mask, void* stream)
 {
@@ -554,17 +534,12 @@ int cs_replay_push(cs_replay* r, int32_t T, const cs_traj_out* traj, uint32_t se
     if (entries > 0x7FFFFFFF) return fail(CS_E_INVALID, "cs_replay_push: window too large (T * n must stay below 2^31)");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    if (entries > r->entries) {
-        if (r->scratch) (void)hipFree(r->scratch);
-        r->scratch = nullptr;
-        r->entries = 0;
-        hipError_t e = hipMalloc((void**)&r->scratch, (size_t)entries * 2 * sizeof(int32_t));
-        if (e != hipSuccess) return fail_hip(e, "cs_replay_push");
-        r->entries = entries;
-    }
-    hipError_t e = cs::launch_replay_push(r->h->b, r->r, T, *traj, seat_mask, r->scratch, r->scratch + r->entries,
-                                          &r->scan_tmp, &r->scan_bytes, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_push");
+    hipError_t e = r->scratch.reserve((size_t)entries * 2 * sizeof(int32_t));
+    if (e != hipSuccess) return done(e, "cs_replay_push");
+    // code, and pos in the second half of what is allocated (the largest push so far)
+    int32_t *code = (int32_t*)r->scratch.p, *pos = code + r->scratch.bytes / (2 * sizeof(int32_t));
+    e = cs::launch_replay_push(r->h->b, r->r, T, *traj, seat_mask, code, pos, r->scan, (hipStream_t)stream);
+    return done(e, "cs_replay_push");
 }
 
 int cs_replay_drop_pending(cs_replay* r, void* stream)
@@ -572,8 +547,8 @@ int cs_replay_drop_pending(cs_replay* r, void* stream)
     if (!r) return fail(CS_E_INVALID, "null argument");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    hipError_t e = hipMemsetAsync(r->r.pvalid, 0, (size_t)(r->h->b.n * r->r.P), (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_drop_pending");
+    return done(hipMemsetAsync(r->r.pvalid, 0, (size_t)(r->h->b.n * r->r.P), (hipStream_t)stream),
+                               "cs_replay_drop_pending");
 }
 
 int cs_replay_size(cs_replay* r, int64_t* size, int64_t* total)
@@ -598,8 +573,7 @@ int cs_replay_gather(cs_replay* r, const int64_t* idx, int64_t B, const cs_repla
     if (B > 0x7FFFFFFF / 32) return fail(CS_E_INVALID, "B out of range");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    hipError_t e = cs::launch_replay_gather(r->r, idx, B, *out, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_replay_gather");
+    return done(cs::launch_replay_gather(r->r, idx, B, *out, (hipStream_t)stream), "cs_replay_gather");
 }
 
 int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* next_legal, const float* reward,
@@ -611,10 +585,8 @@ int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* 
     if (num_actions <= 0) return fail(CS_E_INVALID, "num_actions must be positive");
     if (B < 0 || B > 0x7FFFFFFF) return fail(CS_E_INVALID, "B out of range");
     if (B == 0) return CS_OK;
-    hipError_t e = cs::launch_dqn_targets(q_next, q_next_target, (const uint8_t*)next_legal, reward,
-                                          (const uint8_t*)done, B, num_actions, gamma, target, best,
-                                          (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_dqn_targets");
+    return ::done(cs::launch_dqn_targets(q_next, q_next_target, (const uint8_t*)next_legal, reward, (const uint8_t*)done,
+                                         B, num_actions, gamma, target, best, (hipStream_t)stream), "cs_dqn_targets");
 }
 
 // ---- NFSP ---------------------------------------------------------------------------------------------------------
@@ -626,9 +598,8 @@ int cs_pnet_probs(cs_handle* h, const cs_qnet* net, const void* obs, const void*
     if (!probs) return fail(CS_E_INVALID, "null argument");
     if (rows == 0) return CS_OK;
     if ((r = set_device(h)) != CS_OK) return r;
-    hipError_t e = cs::launch_pnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0, 0, 0, nullptr,
-                                   probs, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_pnet_probs");
+    return done(cs::launch_pnet(*net, (const uint8_t*)obs, (const uint8_t*)legal, nullptr, rows, 0, 0, 0, nullptr,
+                                probs, (hipStream_t)stream), "cs_pnet_probs");
 }
 
 int64_t cs_nfsp_scratch_bytes(int64_t rows)
@@ -657,18 +628,12 @@ int cs_nfsp_actions(cs_handle* h, const cs_qnet* qnet, const cs_qnet* pnet, cons
         e = cs::launch_nfsp_actions(*qnet, *pnet, (const uint8_t*)obs, (const uint8_t*)legal, (const uint8_t*)done,
                                     (const uint8_t*)mode, rows, eps, seed, t, row_base, actions, probs, scratch,
                                     (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_nfsp_actions");
+    return ::done(e, "cs_nfsp_actions");
 }
 
-struct cs_reservoir {
-    cs_handle* h;
-    cs::Reservoir r;
-    void* mem;          // one allocation for the slots, the occupant words and the counter
-    size_t tail;        // bytes from the occupant words to the end of mem (what clear zeroes)
-    int32_t* pos;       // scan output of a push, [entries] (grown on demand)
-    int64_t entries;
-    void* scan_tmp;
-    size_t scan_bytes;
+struct cs_reservoir : cs_sub {   // mem: the slots, the occupant words and the counter; scratch: i32 [entries], the scan
+    cs::Reservoir r;             // output of a push
+    size_t tail;                 // bytes from the occupant words to the end of mem (what clear zeroes)
 };
 
 int cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reservoir** out)
@@ -681,37 +646,20 @@ int cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reserv
     int rc = set_device(h);
     if (rc != CS_OK) return rc;
     const int64_t O = info.obs_dim, cap = capacity;
-    auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
-    const int64_t o_st = 0, o_act = o_st + al(cap * O), o_occ = o_act + al(cap * 4), o_calls = o_occ + al(cap * 8),
-                  total = o_calls + 256;
-    cs_reservoir* p = new (std::nothrow) cs_reservoir();
-    if (!p) return fail(CS_E_INVALID, "out of host memory");
-    hipError_t e = hipMalloc(&p->mem, (size_t)total);
-    if (e != hipSuccess) { delete p; return fail_hip(e, "cs_reservoir_create"); }
-    uint8_t* m = (uint8_t*)p->mem;
-    e = hipMemset(m, 0, (size_t)total);
-    if (e != hipSuccess) { (void)hipFree(p->mem); delete p; return fail_hip(e, "cs_reservoir_create"); }
-    p->h = h;
+    cs::Carve c;
+    const size_t o_st = c.take<uint8_t>(cap * O), o_act = c.take<int32_t>(cap),
+                 o_occ = c.take<unsigned long long>(cap), o_calls = c.take<int64_t>(1);
+    cs_reservoir* p = nullptr;
+    if ((rc = sub_create(h, c.bytes(), 0, "cs_reservoir_create", &p)) != CS_OK) return rc;
+    uint8_t* m = (uint8_t*)p->mem.p;
     p->r = cs::Reservoir{cap, (int32_t)O, info.num_players, info.num_actions, info.action_bytes, seed, m + o_st,
                          (int32_t*)(m + o_act), (unsigned long long*)(m + o_occ), (int64_t*)(m + o_calls)};
-    p->tail = (size_t)(total - o_occ);
-    p->pos = nullptr;
-    p->entries = 0;
-    p->scan_tmp = nullptr;
-    p->scan_bytes = 0;
+    p->tail = c.bytes() - o_occ;
     *out = p;
     return CS_OK;
 }
 
-void cs_reservoir_destroy(cs_reservoir* r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->h->device);
-    if (r->mem) (void)hipFree(r->mem);
-    if (r->pos) (void)hipFree(r->pos);
-    if (r->scan_tmp) (void)hipFree(r->scan_tmp);
-    delete r;
-}
+void cs_reservoir_destroy(cs_reservoir* r) { sub_destroy(r); }
 
 int cs_reservoir_push(cs_reservoir* r, int32_t T, const cs_traj_out* traj, const void* mode, uint32_t seat_mask,
                       void* stream)
@@ -725,18 +673,12 @@ int cs_reservoir_push(cs_reservoir* r, int32_t T, const cs_traj_out* traj, const
         return fail(CS_E_INVALID, "cs_reservoir_push: window too large (T * n must stay below 2^31)");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    if (entries > r->entries) {
-        if (r->pos) (void)hipFree(r->pos);
-        r->pos = nullptr;
-        r->entries = 0;
-        hipError_t e = hipMalloc((void**)&r->pos, (size_t)entries * sizeof(int32_t));
-        if (e != hipSuccess) return fail_hip(e, "cs_reservoir_push");
-        r->entries = entries;
-    }
-    hipError_t e = cs::launch_reservoir_push(r->r, T, r->h->b.n, (const uint8_t*)traj->obs,
-                                             (const uint8_t*)traj->player, traj->action, (const uint8_t*)mode,
-                                             seat_mask, r->pos, &r->scan_tmp, &r->scan_bytes, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_push");
+    hipError_t e = r->scratch.reserve((size_t)entries * sizeof(int32_t));
+    if (e == hipSuccess)
+        e = cs::launch_reservoir_push(r->r, T, r->h->b.n, (const uint8_t*)traj->obs, (const uint8_t*)traj->player,
+                                      traj->action, (const uint8_t*)mode, seat_mask, (int32_t*)r->scratch.p, r->scan,
+                                      (hipStream_t)stream);
+    return done(e, "cs_reservoir_push");
 }
 
 int cs_reservoir_size(cs_reservoir* r, int64_t* size, int64_t* add_calls)
@@ -761,8 +703,7 @@ int cs_reservoir_gather(cs_reservoir* r, const int64_t* idx, int64_t B, float* s
     if (B > 0x7FFFFFFF / 32) return fail(CS_E_INVALID, "B out of range");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    hipError_t e = cs::launch_reservoir_gather(r->r, idx, B, state, probs, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_gather");
+    return done(cs::launch_reservoir_gather(r->r, idx, B, state, probs, (hipStream_t)stream), "cs_reservoir_gather");
 }
 
 int cs_reservoir_clear(cs_reservoir* r, void* stream)
@@ -770,8 +711,7 @@ int cs_reservoir_clear(cs_reservoir* r, void* stream)
     if (!r) return fail(CS_E_INVALID, "null argument");
     int rc = set_device(r->h);
     if (rc != CS_OK) return rc;
-    hipError_t e = hipMemsetAsync(r->r.occ, 0, r->tail, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_reservoir_clear");
+    return done(hipMemsetAsync(r->r.occ, 0, r->tail, (hipStream_t)stream), "cs_reservoir_clear");
 }
 
 int cs_traj_probe(cs_handle* h, int32_t T, const cs_traj_out* out, void* stream)
@@ -783,9 +723,8 @@ int cs_traj_probe(cs_handle* h, int32_t T, const cs_traj_out* out, void* stream)
     int r = set_device(h);
     if (r != CS_OK) return r;
     const cs_game_info& info = h->ops->info;   // envs_per_wave: the game's rollout kernel's (G::EPW)
-    hipError_t e = cs::launch_traj_probe(h->b, T, *out, info.obs_dim, info.legal_bytes, info.action_bytes,
-                                         info.envs_per_wave, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_traj_probe");
+    return done(cs::launch_traj_probe(h->b, T, *out, info.obs_dim, info.legal_bytes, info.action_bytes,
+                                      info.envs_per_wave, (hipStream_t)stream), "cs_traj_probe");
 }
 
 int cs_state_bytes(const cs_handle* h, int64_t* bytes)
@@ -830,8 +769,7 @@ int cs_transitions(cs_handle* h, int32_t T, const cs_traj_out* traj, const cs_tr
     if (T <= 0) return fail(CS_E_INVALID, "T must be positive");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_transitions(h->b, T, *traj, *out, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_transitions");
+    return done(cs::launch_transitions(h->b, T, *traj, *out, (hipStream_t)stream), "cs_transitions");
 }
 
 int cs_legal_lists(cs_handle* h, const void* legal, int64_t rows, int32_t* counts, int64_t* offsets, int32_t* ids,
@@ -841,9 +779,8 @@ int cs_legal_lists(cs_handle* h, const void* legal, int64_t rows, int32_t* count
     if (rows <= 0 || rows > ((int64_t)1 << 31) - 1) return fail(CS_E_INVALID, "rows out of range");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_legal_lists(h->b, h->ops->info.legal_bytes, (const uint8_t*)legal, rows, counts, offsets,
-                                          ids, &h->scan_tmp, &h->scan_bytes, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_legal_lists");
+    return done(cs::launch_legal_lists(h->b, h->ops->info.legal_bytes, (const uint8_t*)legal, rows, counts, offsets,
+                                       ids, h->scan, (hipStream_t)stream), "cs_legal_lists");
 }
 
 int cs_action_features(cs_handle* h, const int32_t* ids, int64_t count, void* features, void* stream)
@@ -853,13 +790,14 @@ int cs_action_features(cs_handle* h, const int32_t* ids, int64_t count, void* fe
     int r = set_device(h);
     if (r != CS_OK) return r;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = h->b.game == CS_GAME_DOUDIZHU
-                       ? cs::ddz::launch_features(h->b, ids, count, (uint8_t*)features, s)
-                       : cs::launch_onehot(ids, count, h->ops->info.num_actions, (uint8_t*)features, s);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_action_features");
+    return done(h->b.game == CS_GAME_DOUDIZHU ? cs::ddz::launch_features(h->b, ids, count, (uint8_t*)features,
+                                                                         s) : cs::launch_onehot(ids, count,
+                                                                         h->ops->info.num_actions, (uint8_t*)features,
+                                                                         s), "cs_action_features");
 }
 
-int cs_get_env_state(cs_handle* h, int64_t env, uint32_t* host_words, int32_t nwords)
+// cs_get_env_state (to_host) / cs_set_env_state: env's packed state words between the device and host_words
+static int env_state_copy(cs_handle* h, int64_t env, uint32_t* host_words, int32_t nwords, bool to_host)
 {
     if (!h || !host_words) return fail(CS_E_INVALID, "null argument");
     if (env < 0 || env >= h->b.n || nwords < h->ops->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
@@ -867,15 +805,22 @@ int cs_get_env_state(cs_handle* h, int64_t env, uint32_t* host_words, int32_t nw
     if (r != CS_OK) return r;
     hipError_t e = hipDeviceSynchronize();
     const int sw = h->ops->info.state_words;
+    auto copy = [&](uint32_t* dev, uint32_t* host, int words) {
+        return to_host ? hipMemcpy(host, dev, sizeof(uint32_t) * words, hipMemcpyDeviceToHost)
+                       : hipMemcpy(dev, host, sizeof(uint32_t) * words, hipMemcpyHostToDevice);
+    };
     if (h->ops->env_major) {
-        if (e == hipSuccess)
-            e = hipMemcpy(host_words, h->b.state + (size_t)env * sw, sizeof(uint32_t) * sw, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = copy(h->b.state + (size_t)env * sw, host_words, sw);
     } else {
         for (int w = 0; w < sw && e == hipSuccess; w++)
-            e = hipMemcpy(host_words + w, h->b.state + (size_t)w * h->b.n + env, sizeof(uint32_t),
-                          hipMemcpyDeviceToHost);
+            e = copy(h->b.state + (size_t)w * h->b.n + env, host_words + w, 1);
     }
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_get_env_state");
+    return done(e, to_host ? "cs_get_env_state" : "cs_set_env_state");
+}
+
+int cs_get_env_state(cs_handle* h, int64_t env, uint32_t* host_words, int32_t nwords)
+{
+    return env_state_copy(h, env, host_words, nwords, true);
 }
 
 int cs_copy_env_state(cs_handle* h, int64_t env, uint32_t* dst, void* stream)
@@ -885,28 +830,13 @@ int cs_copy_env_state(cs_handle* h, int64_t env, uint32_t* dst, void* stream)
     if (h->ops->info.state_words > 64) return fail(CS_E_UNSUPPORTED, "state too large for cs_copy_env_state");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::launch_copy_state(h->b, env, h->ops->info.state_words, h->ops->env_major ? 1 : 0, dst,
-                                         (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_copy_env_state");
+    return done(cs::launch_copy_state(h->b, env, h->ops->info.state_words, h->ops->env_major ? 1 : 0, dst,
+                                      (hipStream_t)stream), "cs_copy_env_state");
 }
 
 int cs_set_env_state(cs_handle* h, int64_t env, const uint32_t* host_words, int32_t nwords)
 {
-    if (!h || !host_words) return fail(CS_E_INVALID, "null argument");
-    if (env < 0 || env >= h->b.n || nwords < h->ops->info.state_words) return fail(CS_E_INVALID, "bad env or nwords");
-    int r = set_device(h);
-    if (r != CS_OK) return r;
-    hipError_t e = hipDeviceSynchronize();
-    const int sw = h->ops->info.state_words;
-    if (h->ops->env_major) {
-        if (e == hipSuccess)
-            e = hipMemcpy(h->b.state + (size_t)env * sw, host_words, sizeof(uint32_t) * sw, hipMemcpyHostToDevice);
-    } else {
-        for (int w = 0; w < sw && e == hipSuccess; w++)
-            e = hipMemcpy(h->b.state + (size_t)w * h->b.n + env, host_words + w, sizeof(uint32_t),
-                          hipMemcpyHostToDevice);
-    }
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_set_env_state");
+    return env_state_copy(h, env, const_cast<uint32_t*>(host_words), nwords, false);
 }
 
 int cs_env_rng_words(cs_handle* h, int32_t* words)
@@ -925,7 +855,7 @@ static int rng_copy(cs_handle* h, int64_t env, uint32_t* buf, int32_t load, void
     const uint32_t clear = h->b.sbuf ? (1u << 17) : 0u;   // restored streams restage from the ring
     hipError_t e = cs::launch_rng_copy(h->b, env, h->ops->mt_words, h->ops->mt_columns ? 1 : 0, clear, buf, load,
                                        (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, what);
+    return done(e, what);
 }
 
 int cs_copy_env_rng(cs_handle* h, int64_t env, uint32_t* dst, void* stream)
@@ -946,15 +876,14 @@ int cs_get_rng_ctl(cs_handle* h, int64_t env, uint32_t* host_ctl)
     if (r != CS_OK) return r;
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(host_ctl, h->b.ctl + env, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_get_rng_ctl");
+    return done(e, "cs_get_rng_ctl");
 }
 
 int cs_debug_holdem_rank7(const int8_t* cards, int64_t n, uint32_t* values, void* stream)
 {
     if (!cards || !values) return fail(CS_E_INVALID, "null argument");
     if (n <= 0 || n > ((int64_t)1 << 31)) return fail(CS_E_INVALID, "n out of range");
-    hipError_t e = cs::launch_debug_rank7(cards, n, values, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_debug_holdem_rank7");
+    return done(cs::launch_debug_rank7(cards, n, values, (hipStream_t)stream), "cs_debug_holdem_rank7");
 }
 
 int cs_debug_ddz_legal(cs_handle* h, const uint8_t* counts, const int32_t* prev, int64_t n, uint8_t* legal,
@@ -965,8 +894,7 @@ int cs_debug_ddz_legal(cs_handle* h, const uint8_t* counts, const int32_t* prev,
     if (n <= 0 || n > ((int64_t)1 << 31)) return fail(CS_E_INVALID, "n out of range");
     int r = set_device(h);
     if (r != CS_OK) return r;
-    hipError_t e = cs::ddz::launch_debug_legal(h->b, counts, prev, n, legal, (hipStream_t)stream);
-    return e == hipSuccess ? CS_OK : fail_hip(e, "cs_debug_ddz_legal");
+    return done(cs::ddz::launch_debug_legal(h->b, counts, prev, n, legal, (hipStream_t)stream), "cs_debug_ddz_legal");
 }
 
 int cs_debug_set_serial_refill(cs_handle* h, int32_t enable)

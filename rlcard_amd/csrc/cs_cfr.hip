@@ -262,11 +262,9 @@ __global__ void k_cfr_reduce(const uint16_t* __restrict__ key, const uint32_t* _
     t.avg[i] = v;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
-hipError_t launch_cfr(const Buffers& b, int32_t iterations, int64_t iteration0, const CfrTables& t, CfrScratch* sc,
+hipError_t launch_cfr(const Buffers& b, int32_t iterations, int64_t iteration0, const CfrTables& t, DevBuf& scratch,
                       hipStream_t s)
 {
     const dim3 grid((unsigned)((b.n + 255) / 256)), ugrid((CFR_NI + 255) / 256);
@@ -283,19 +281,13 @@ hipError_t launch_cfr(const Buffers& b, int32_t iterations, int64_t iteration0, 
         e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint16_t*)nullptr, (uint16_t*)nullptr,
                                                (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)m, 0, 12, s);
         if (e != hipSuccess) return e;
-        const size_t o_val = 0, o_key = al256(o_val + (size_t)m * 64), o_kout = al256(o_key + (size_t)m * 2),
-                     o_sin = al256(o_kout + (size_t)m * 2), o_sout = al256(o_sin + (size_t)m * 4),
-                     o_seg = al256(o_sout + (size_t)m * 4), o_tmp = al256(o_seg + (size_t)CFR_NI * 8),
-                     total = o_tmp + sort_bytes;
-        const bool fresh = sc->bytes < total;
-        if (fresh) {
-            if (sc->mem) (void)hipFree(sc->mem);
-            sc->mem = nullptr;
-            sc->bytes = 0;
-            if ((e = hipMalloc(&sc->mem, total)) != hipSuccess) return e;
-            sc->bytes = total;
-        }
-        uint8_t* base = (uint8_t*)sc->mem;
+        Carve c;
+        const size_t o_val = c.take<double>((size_t)m * 8), o_key = c.take<uint16_t>((size_t)m),
+                     o_kout = c.take<uint16_t>((size_t)m), o_sin = c.take<uint32_t>((size_t)m),
+                     o_sout = c.take<uint32_t>((size_t)m), o_seg = c.take<int32_t>((size_t)CFR_NI * 2),
+                     o_tmp = c.bytes();
+        if ((e = scratch.reserve(o_tmp + sort_bytes)) != hipSuccess) return e;
+        uint8_t* base = (uint8_t*)scratch.p;
         recs.val = (double*)(base + o_val);
         recs.key = (uint16_t*)(base + o_key);
         key_out = (uint16_t*)(base + o_kout);

@@ -454,4 +454,28 @@ __device__ __forceinline__ void set_bit(uint32_t (&bits)[NB], int p)
     for (int j = 0; j < NB; j++) bits[j] |= ((p >> 5) == j) ? (1u << (p & 31)) : 0u;
 }
 
+// ---- the agents' buffer kernels (cs_dmc.hip, cs_dqn.hip, cs_nfsp.hip) ----------------------------------------------
+// row `row` of a trajectory's action tensor: u8 or i16, by cs_game_info.action_bytes
+__device__ __forceinline__ int traj_action(const void* action, int abytes, int64_t row)
+{
+    return abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+}
+
+// thread i of a grid with one thread per (row, 4 bytes of the row's O): its row and first byte column; false past the
+// last row
+__device__ __forceinline__ bool row_col4(int64_t i, int64_t rows, int O, int64_t& row, int& col)
+{
+    const int q4 = (O + 3) / 4;
+    if (i >= rows * q4) return false;
+    row = i / q4;
+    col = (int)(i - row * q4) * 4;
+    return true;
+}
+
+// a caller's gather index brought into [0, size) (0 when the buffer is empty), so the kernel reads inside the buffer
+__device__ __forceinline__ int64_t clamp_index(int64_t x, int64_t size)
+{
+    return x < 0 ? 0 : (x >= size ? (size > 0 ? size - 1 : 0) : x);
+}
+
 }  // namespace cs

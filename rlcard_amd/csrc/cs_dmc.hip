@@ -17,9 +17,9 @@
 //                  bias and ReLU. The 512-wide hidden layers are plain GEMMs (torch, hipBLASLt). k_dmc_select is the
 //                  per-state argmax (np.argmax: first maximum) with the epsilon-greedy branch of DMCAgent.step.
 // All streaming integer / fp32 work, HBM-bound: no MFMA in these kernels (the GEMMs between them are hipBLASLt's).
-#include <hipcub/hipcub.hpp>
 #include "cs_device.h"
 #include "cs_engine.h"
+#include "cs_scan.h"
 #include "cs_doudizhu.h"
 
 namespace cs {
@@ -114,11 +114,9 @@ __global__ __launch_bounds__(DBLOCK) void k_dmc_ready(const int32_t* __restrict_
 __global__ __launch_bounds__(DBLOCK) void k_dmc_rows(const uint8_t* __restrict__ obs, const int64_t* __restrict__ dst,
                                                      int64_t rows, int O, int8_t* st)
 {
-    const int q4 = (O + 3) / 4;
-    const int64_t i = (int64_t)blockIdx.x * DBLOCK + threadIdx.x;
-    if (i >= rows * q4) return;
-    const int64_t row = i / q4;
-    const int c = (int)(i - row * q4) * 4;
+    int64_t row;
+    int c;
+    if (!row_col4((int64_t)blockIdx.x * DBLOCK + threadIdx.x, rows, O, row, c)) return;
     const int64_t r = dst[row];
     if (r < 0) return;
     const uint8_t* src = obs + row * O + c;
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(DBLOCK) void k_dmc_features(const void* __restrict_
     if (row >= rows) return;
     const int64_t r = dst[row];
     if (r < 0) return;
-    const int a = abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+    const int a = traj_action(action, abytes, row);
     int8_t* d = act + r * F;
     if (ddz_cnt) {
         const uint64_t bits = ddz::cards_bits(a >= 0 && a < ddz::PASS ? ddz_cnt[a] : 0ull);
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(DBLOCK) void k_dmc_gather(const int64_t* __restrict
 }
 
 hipError_t launch_dmc_fill(const Buffers& b, const DmcRing& d, int32_t T, const cs_traj_out& tr, int64_t* ready,
-                           int64_t cap, int64_t* nready, int64_t* dst, void** tmp, size_t* tmp_bytes, hipStream_t s)
+                           int64_t cap, int64_t* nready, int64_t* dst, DevBuf& scan, hipStream_t s)
 {
     const int64_t streams = b.n * b.num_players, rows = (int64_t)T * b.n;
     hipLaunchKernelGGL(k_dmc_index, dim3((unsigned)((b.n + DBLOCK - 1) / DBLOCK)), dim3(DBLOCK), 0, s,
@@ -179,20 +177,8 @@ hipError_t launch_dmc_fill(const Buffers& b, const DmcRing& d, int32_t T, const 
                        d.flag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    size_t need = 0;
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, d.counts, d.offsets, streams + 1, s);
-    if (e != hipSuccess) return e;
-    if (need > *tmp_bytes) {
-        if (*tmp) (void)hipFree(*tmp);
-        *tmp = nullptr;
-        *tmp_bytes = 0;
-        e = hipMalloc(tmp, need);
-        if (e != hipSuccess) return e;
-        *tmp_bytes = need;
-    }
     // counts[streams] is kept 0, so offsets[streams] is the total
-    e = hipcub::DeviceScan::ExclusiveSum(*tmp, need, d.counts, d.offsets, streams + 1, s);
-    if (e != hipSuccess) return e;
+    if ((e = scan_sum(scan, d.counts, d.offsets, streams + 1, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_dmc_ready, dim3((unsigned)((streams + DBLOCK - 1) / DBLOCK)), dim3(DBLOCK), 0, s, d.counts,
                        d.offsets, streams, d.slots, d.emitted, ready, cap, nready, d.flag);
     if (tr.obs) {

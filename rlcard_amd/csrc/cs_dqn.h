@@ -51,15 +51,14 @@ struct Reservoir {
 };
 // pos: [T * n + 1] i32 scratch of the push (grown by the caller)
 hipError_t launch_reservoir_push(const Reservoir& r, int32_t T, int64_t n, const uint8_t* obs, const uint8_t* player,
-                                 const void* action, const uint8_t* mode, uint32_t seat_mask, int32_t* pos, void** tmp,
-                                 size_t* tmp_bytes, hipStream_t s);
+                                 const void* action, const uint8_t* mode, uint32_t seat_mask, int32_t* pos, DevBuf& scan,
+                                 hipStream_t s);
 hipError_t launch_reservoir_gather(const Reservoir& r, const int64_t* idx, int64_t B, float* state, float* probs,
                                    hipStream_t s);
 
 // code: [n * P + T * n + 1] i32, pos: the same length (scratch of the push, grown by the caller)
 hipError_t launch_replay_push(const Buffers& b, const ReplayRing& r, int32_t T, const cs_traj_out& tr,
-                              uint32_t seat_mask, int32_t* code, int32_t* pos, void** tmp, size_t* tmp_bytes,
-                              hipStream_t s);
+                              uint32_t seat_mask, int32_t* code, int32_t* pos, DevBuf& scan, hipStream_t s);
 hipError_t launch_replay_gather(const ReplayRing& r, const int64_t* idx, int64_t B, const cs_replay_batch& o,
                                 hipStream_t s);
 hipError_t launch_dqn_targets(const float* q_next, const float* q_next_target, const uint8_t* next_legal,

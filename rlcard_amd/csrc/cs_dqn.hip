@@ -27,10 +27,10 @@
 //                     a later push. Write positions come from one prefix sum over [pending (env, seat)] + [rows (t, env)].
 //   k_replay_gather   Memory.sample's stacking, u8 -> f32 fused.
 //   k_dqn_targets     dqn_agent.py:205-218: Double-DQN best next action and target, each operation rounded to fp32.
-#include <hipcub/hipcub.hpp>
 #include <math.h>
 #include "cs_device.h"
 #include "cs_dqn.h"
+#include "cs_scan.h"
 
 namespace cs {
 
@@ -376,12 +376,12 @@ hipError_t launch_nfsp_actions(const cs_qnet& qnet, const cs_qnet& pnet, const u
     int32_t* list0 = pos + rows;
     int32_t* list1 = list0 + rows;
     int32_t* counts = list1 + rows;
-    void* tmp = (uint8_t*)scratch + nfsp_lists_bytes(rows);
-    hipcub::TransformInputIterator<int32_t, ModeFlag, const uint8_t*> flags(mode, ModeFlag());
-    size_t need = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags, pos, (int)rows, s);
+    size_t total = 0;   // the caller's scratch, by the contract of nfsp_scratch_bytes
+    hipError_t e = nfsp_scratch_bytes(rows, &total);
     if (e != hipSuccess) return e;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, need, flags, pos, (int)rows, s)) != hipSuccess) return e;
+    const size_t lists = nfsp_lists_bytes(rows);
+    hipcub::TransformInputIterator<int32_t, ModeFlag, const uint8_t*> flags(mode, ModeFlag());
+    if ((e = scan_sum((uint8_t*)scratch + lists, total - lists, flags, pos, (int)rows, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_row_lists, dim3((unsigned)((rows + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, mode, rows, pos,
                        list0, list1, counts);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -457,12 +457,11 @@ __global__ __launch_bounds__(QBLOCK) void k_replay_write(ReplayRing r, int T, in
                                                          const int32_t* __restrict__ code,
                                                          const int32_t* __restrict__ pos)
 {
-    const int O = r.O, P = r.P, q4 = (O + 3) / 4;
+    const int O = r.O, P = r.P;
     const int64_t NP = n * P, M = NP + (int64_t)T * n;
-    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
-    if (i >= M * q4) return;
-    const int64_t j = i / q4;
-    const int c0 = (int)(i - j * q4) * 4;
+    int64_t j;
+    int c0;
+    if (!row_col4((int64_t)blockIdx.x * QBLOCK + threadIdx.x, M, O, j, c0)) return;
     const int32_t c = code[j];
     if (!(c >= 0 || c <= -3)) return;
     const int64_t fresh = pos[M], at = pos[j];
@@ -481,7 +480,7 @@ __global__ __launch_bounds__(QBLOCK) void k_replay_write(ReplayRing r, int T, in
         e = row % n;
         p = player[row];
         s_src = obs + row * O;
-        a = r.abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+        a = traj_action(action, r.abytes, row);
     }
     const bool ended = c < 0;
     const int64_t nrow = (int64_t)(ended ? -3 - c : c) * n + e;
@@ -508,13 +507,13 @@ __global__ __launch_bounds__(QBLOCK) void k_replay_carry(ReplayRing r, int T, in
                                                          const int32_t* __restrict__ code,
                                                          const int32_t* __restrict__ pos)
 {
-    const int O = r.O, q4 = (O + 3) / 4;
+    const int O = r.O;
     const int64_t NP = n * r.P;
     const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
     if (i == 0) *r.total += pos[NP + (int64_t)T * n];
-    if (i >= NP * q4) return;
-    const int64_t j = i / q4;
-    const int c0 = (int)(i - j * q4) * 4;
+    int64_t j;
+    int c0;
+    if (!row_col4(i, NP, O, j, c0)) return;
     const int32_t t = r.newpend[j];
     if (t < 0) {
         const int32_t c = code[j];
@@ -526,14 +525,13 @@ __global__ __launch_bounds__(QBLOCK) void k_replay_carry(ReplayRing r, int T, in
     for (int k = 0; k < 4; k++)
         if (c0 + k < O) r.pst[j * O + c0 + k] = obs[row * O + c0 + k];
     if (c0 == 0) {
-        r.pact[j] = r.abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+        r.pact[j] = traj_action(action, r.abytes, row);
         r.pvalid[j] = 1;
     }
 }
 
 hipError_t launch_replay_push(const Buffers& b, const ReplayRing& r, int32_t T, const cs_traj_out& tr,
-                              uint32_t seat_mask, int32_t* code, int32_t* pos, void** tmp, size_t* tmp_bytes,
-                              hipStream_t s)
+                              uint32_t seat_mask, int32_t* code, int32_t* pos, DevBuf& scan, hipStream_t s)
 {
     const int64_t n = b.n, NP = n * r.P, M = NP + (int64_t)T * n;
     const int q4 = (r.O + 3) / 4;
@@ -543,16 +541,7 @@ hipError_t launch_replay_push(const Buffers& b, const ReplayRing& r, int32_t T, 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipcub::TransformInputIterator<int32_t, ReplayCount, const int32_t*> counts(code, ReplayCount());
-    size_t need = 0;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, counts, pos, (int)(M + 1), s)) != hipSuccess) return e;
-    if (need > *tmp_bytes) {
-        if (*tmp) (void)hipFree(*tmp);
-        *tmp = nullptr;
-        *tmp_bytes = 0;
-        if ((e = hipMalloc(tmp, need)) != hipSuccess) return e;
-        *tmp_bytes = need;
-    }
-    if ((e = hipcub::DeviceScan::ExclusiveSum(*tmp, need, counts, pos, (int)(M + 1), s)) != hipSuccess) return e;
+    if ((e = scan_sum(scan, counts, pos, (int)(M + 1), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_replay_write, dim3((unsigned)((M * q4 + QBLOCK - 1) / QBLOCK)), dim3(QBLOCK), 0, s, r, T, n,
                        (const uint8_t*)tr.obs, (const uint8_t*)tr.legal, (const uint8_t*)tr.player, tr.action,
                        (const float*)tr.reward, (const uint8_t*)tr.final_obs, code, pos);
@@ -568,15 +557,12 @@ __global__ __launch_bounds__(QBLOCK) void k_replay_gather(ReplayRing r, const in
                                                           float* o_st, int64_t* o_act, float* o_rew, float* o_nst,
                                                           uint8_t* o_nlg, uint8_t* o_dne)
 {
-    const int O = r.O, q4 = (O + 3) / 4;
-    const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
-    if (i >= B * q4) return;
-    const int64_t k = i / q4;
-    const int c0 = (int)(i - k * q4) * 4;
+    const int O = r.O;
+    int64_t k;
+    int c0;
+    if (!row_col4((int64_t)blockIdx.x * QBLOCK + threadIdx.x, B, O, k, c0)) return;
     const int64_t total = *r.total, size = total < r.cap ? total : r.cap;
-    int64_t x = idx[k];
-    x = x < 0 ? 0 : (x >= size ? (size > 0 ? size - 1 : 0) : x);
-    const int64_t slot = (total - size + x) % r.cap;
+    const int64_t slot = (total - size + clamp_index(idx[k], size)) % r.cap;
 #pragma unroll
     for (int u = 0; u < 4; u++) {
         if (c0 + u < O) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cardsim.h"
+#include "cs_devbuf.h"
 
 namespace cs {
 
@@ -92,7 +93,7 @@ const GameOps* find_blackjack_shoe(int32_t num_players, int32_t num_decks, int32
 
 // cs_dmc.hip
 hipError_t launch_dmc_fill(const Buffers& b, const DmcRing& d, int32_t T, const cs_traj_out& tr, int64_t* ready,
-                           int64_t cap, int64_t* nready, int64_t* dst, void** tmp, size_t* tmp_bytes, hipStream_t s);
+                           int64_t cap, int64_t* nready, int64_t* dst, DevBuf& scan, hipStream_t s);
 hipError_t launch_dmc_gather(const DmcRing& d, int32_t state_dim, int32_t obs_dim, const int64_t* chunks,
                              int64_t count, const cs_dmc_batch& o, hipStream_t s);
 hipError_t launch_dmc_layer1(const float* X, const int32_t* state_of, const int32_t* ids, int64_t E, int32_t H,
@@ -109,12 +110,8 @@ struct CfrTables {
     double* regrets;
     uint32_t* flags;
 };
-// batched mode (n > 1): the deals' table contributions, reduced in a fixed order (cs_cfr.hip); handle-owned
-struct CfrScratch {
-    void* mem;      // one allocation, grown on demand
-    size_t bytes;
-};
-hipError_t launch_cfr(const Buffers& b, int32_t iterations, int64_t iteration0, const CfrTables& t, CfrScratch* sc,
+// scratch (batched mode, n > 1): the deals' table contributions, reduced in a fixed order (cs_cfr.hip); handle-owned
+hipError_t launch_cfr(const Buffers& b, int32_t iterations, int64_t iteration0, const CfrTables& t, DevBuf& scratch,
                       hipStream_t s);
 
 // cs_traj.hip
@@ -125,7 +122,7 @@ hipError_t launch_transitions(const Buffers& b, int32_t T, const cs_traj_out& tr
 hipError_t launch_payoff_sums(const Buffers& b, int32_t T, const cs_traj_out& tr, int32_t quota, int32_t* games_per_env,
                               double* sums, int64_t* games, hipStream_t s);
 hipError_t launch_legal_lists(const Buffers& b, int32_t lb, const uint8_t* legal, int64_t rows, int32_t* counts,
-                              int64_t* offsets, int32_t* ids, void** tmp, size_t* tmp_bytes, hipStream_t s);
+                              int64_t* offsets, int32_t* ids, DevBuf& scan, hipStream_t s);
 hipError_t launch_onehot(const int32_t* ids, int64_t count, int32_t na, uint8_t* out, hipStream_t s);
 hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, int32_t env_major, uint32_t* dst,
                              hipStream_t s);

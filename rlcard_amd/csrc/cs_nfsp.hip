@@ -12,9 +12,9 @@
 //   k_reservoir_write   the candidate whose k + 1 is the slot's word writes its row: one writer per slot, whatever
 //                       the order the threads run in
 //   k_reservoir_gather  slots -> f32 state rows and one-hot action_probs rows
-#include <hipcub/hipcub.hpp>
 #include "cs_device.h"
 #include "cs_dqn.h"
+#include "cs_scan.h"
 
 namespace cs {
 
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(RBLOCK) void k_reservoir_write(Reservoir r, Reservo
     } else {
         for (int u = 0; u < O; u++) dst[u] = src[u];
     }
-    r.act[slot] = r.abytes == 1 ? (int)((const uint8_t*)action)[row] : (int)((const int16_t*)action)[row];
+    r.act[slot] = traj_action(action, r.abytes, row);
 }
 
 __global__ void k_reservoir_advance(Reservoir r, const int32_t* __restrict__ pos, int64_t M)
@@ -86,24 +86,15 @@ __global__ void k_reservoir_advance(Reservoir r, const int32_t* __restrict__ pos
 }
 
 hipError_t launch_reservoir_push(const Reservoir& r, int32_t T, int64_t n, const uint8_t* obs, const uint8_t* player,
-                                 const void* action, const uint8_t* mode, uint32_t seat_mask, int32_t* pos, void** tmp,
-                                 size_t* tmp_bytes, hipStream_t s)
+                                 const void* action, const uint8_t* mode, uint32_t seat_mask, int32_t* pos, DevBuf& scan,
+                                 hipStream_t s)
 {
     const int64_t M = (int64_t)T * n;
     const ReservoirCand cand{player, mode, M, r.P, seat_mask};
     hipcub::CountingInputIterator<int64_t> rows(0);
     hipcub::TransformInputIterator<int32_t, ReservoirCand, hipcub::CountingInputIterator<int64_t>> flags(rows, cand);
-    size_t need = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags, pos, (int)(M + 1), s);
+    hipError_t e = scan_sum(scan, flags, pos, (int)(M + 1), s);
     if (e != hipSuccess) return e;
-    if (need > *tmp_bytes) {
-        if (*tmp) (void)hipFree(*tmp);
-        *tmp = nullptr;
-        *tmp_bytes = 0;
-        if ((e = hipMalloc(tmp, need)) != hipSuccess) return e;
-        *tmp_bytes = need;
-    }
-    if ((e = hipcub::DeviceScan::ExclusiveSum(*tmp, need, flags, pos, (int)(M + 1), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_reservoir_claim, dim3((unsigned)((M + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, s, r, cand, pos);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_reservoir_write, dim3((unsigned)((M + RBLOCK - 1) / RBLOCK)), dim3(RBLOCK), 0, s, r, cand, pos,
@@ -118,14 +109,12 @@ hipError_t launch_reservoir_push(const Reservoir& r, int32_t T, int64_t n, const
 __global__ __launch_bounds__(RBLOCK) void k_reservoir_gather(Reservoir r, const int64_t* __restrict__ idx, int64_t B,
                                                              float* __restrict__ o_st, float* __restrict__ o_pr)
 {
-    const int O = r.O, q4 = (O + 3) / 4;
-    const int64_t i = (int64_t)blockIdx.x * RBLOCK + threadIdx.x;
-    if (i >= B * q4) return;
-    const int64_t k = i / q4;
-    const int c0 = (int)(i - k * q4) * 4;
+    const int O = r.O;
+    int64_t k;
+    int c0;
+    if (!row_col4((int64_t)blockIdx.x * RBLOCK + threadIdx.x, B, O, k, c0)) return;
     const int64_t calls = *r.add_calls, size = calls < r.cap ? calls : r.cap;
-    int64_t slot = idx[k];
-    slot = slot < 0 ? 0 : (slot >= size ? (size > 0 ? size - 1 : 0) : slot);
+    const int64_t slot = clamp_index(idx[k], size);
     if (o_st) {
 #pragma unroll
         for (int u = 0; u < 4; u++)

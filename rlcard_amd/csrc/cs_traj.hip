@@ -4,9 +4,9 @@
 //   k_legal_count / k_legal_fill   legal-action id lists from the bitmask rows (wavefront compaction), the form the
 //                                  agents consume (state['legal_actions'] keys, envs/env.py _extract_state)
 // All HBM-bound streaming: a few bytes per row in and out.
-#include <hipcub/hipcub.hpp>
 #include "cs_device.h"
 #include "cs_engine.h"
+#include "cs_scan.h"
 
 namespace cs {
 
@@ -285,7 +285,7 @@ hipError_t launch_transitions(const Buffers& b, int32_t T, const cs_traj_out& tr
 }
 
 hipError_t launch_legal_lists(const Buffers& b, int32_t lb, const uint8_t* legal, int64_t rows, int32_t* counts,
-                              int64_t* offsets, int32_t* ids, void** tmp, size_t* tmp_bytes, hipStream_t s)
+                              int64_t* offsets, int32_t* ids, DevBuf& scan, hipStream_t s)
 {
     hipError_t e;
     const bool wave = lb > 16;
@@ -296,16 +296,7 @@ hipError_t launch_legal_lists(const Buffers& b, int32_t lb, const uint8_t* legal
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // offsets[0] = 0, offsets[1..rows] = inclusive prefix sum of the counts
     if ((e = hipMemsetAsync(offsets, 0, sizeof(int64_t), s)) != hipSuccess) return e;
-    size_t need = 0;
-    if ((e = hipcub::DeviceScan::InclusiveSum(nullptr, need, counts, offsets + 1, rows, s)) != hipSuccess) return e;
-    if (need > *tmp_bytes) {
-        if (*tmp) (void)hipFree(*tmp);
-        *tmp = nullptr;
-        *tmp_bytes = 0;
-        if ((e = hipMalloc(tmp, need)) != hipSuccess) return e;
-        *tmp_bytes = need;
-    }
-    if ((e = hipcub::DeviceScan::InclusiveSum(*tmp, need, counts, offsets + 1, rows, s)) != hipSuccess) return e;
+    if ((e = scan_sum<true>(scan, counts, offsets + 1, rows, s)) != hipSuccess) return e;
     if (ids) {
         if (wave) hipLaunchKernelGGL(k_legal_wave<true>, g_wave, dim3(TBLOCK), 0, s, legal, rows, lb, nullptr, offsets,
                                      ids);

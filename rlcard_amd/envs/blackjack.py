@@ -33,7 +33,7 @@ class BlackjackEnv(Env):
         self.state_shape = [[2] for _ in range(self.num_players)]
         self.action_shape = [None for _ in range(self.num_players)]
         n = C.c_int32()
-        _abi.check(_abi.lib().cs_env_rng_words(self._vec._h, C.byref(n)), 'cs_env_rng_words')
+        _abi.call('cs_env_rng_words', self._vec._h, C.byref(n))
         self._rng_words = n.value
 
     def seed(self, seed=None):
@@ -45,13 +45,13 @@ class BlackjackEnv(Env):
         io = self._io
         buf = torch.empty(self._rng_words, dtype=torch.int32, device=self._vec.device)
         buf.record_stream(io.stream)
-        _abi.check(_abi.lib().cs_copy_env_rng(self._vec._h, 0, C.c_void_p(buf.data_ptr()), io.st), 'cs_copy_env_rng')
+        _abi.call('cs_copy_env_rng', self._vec._h, 0, _abi.ptr(buf), io.st)
         return buf
 
     def _rng_load(self, buf):
         io = self._io
         buf.record_stream(io.stream)
-        _abi.check(_abi.lib().cs_load_env_rng(self._vec._h, 0, C.c_void_p(buf.data_ptr()), io.st), 'cs_load_env_rng')
+        _abi.call('cs_load_env_rng', self._vec._h, 0, _abi.ptr(buf), io.st)
 
     def _snapshot_extra(self):
         return self._rng_copy()      # deepcopy(self.dealer) holds the dealer's np_random

@@ -80,8 +80,7 @@ class _Io:
         self.obs_out = _abi.StepOut(self.out.obs, self.out.legal, self.out.player, None, self.out.done)
         self.ids_base = self.ids.data_ptr()
         self.vec = vec   # the record stays registered on vec's handle until close()
-        _abi.check(_abi.lib().cs_set_step_record(vec._h, 0, C.c_void_p(base + self.o_words), C.c_void_p(base)),
-                   'cs_set_step_record')
+        _abi.call('cs_set_step_record', vec._h, 0, C.c_void_p(base + self.o_words), C.c_void_p(base))
         self.expect = 0
 
     def act_ptr(self, a):
@@ -158,13 +157,13 @@ class Env(object):
     # -- rlcard Env API ----------------------------------------------------------------------------------------
     def _call(self, kind, arg=0, with_reward=True):
         """One engine call on the env; the kernels write the record into mapped host memory (see _Io)."""
-        io, h, L = self._io, self._vec._h, _abi.lib()
+        io, h = self._io, self._vec._h
         if kind == 'step':
-            _abi.check(L.cs_step(h, io.act_ptr(arg), C.byref(io.out), io.st), 'cs_step')
+            _abi.call('cs_step', h, io.act_ptr(arg), C.byref(io.out), io.st)
         elif kind == 'reset':
-            _abi.check(L.cs_reset(h, C.byref(io.out), io.st), 'cs_reset')
+            _abi.call('cs_reset', h, C.byref(io.out), io.st)
         else:
-            _abi.check(L.cs_observe(h, int(arg), C.byref(io.obs_out), io.st), 'cs_observe')
+            _abi.call('cs_observe', h, int(arg), C.byref(io.obs_out), io.st)
         io.wait()
         out, self._words = io.record(with_reward)
         return out

@@ -38,11 +38,10 @@ def legal_ids(legal_row):
     return [int(i) for i in np.nonzero(b)[0]]
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = _abi.ptr
 
 
-class VecEnv:
+class VecEnv(_abi.Handle):
     def __init__(self, env_id, num_envs, seed=0, seeds=None, device=None, config=None, env_base=0):
         config = dict(config or {})
         self.env_id = env_id
@@ -66,37 +65,20 @@ class VecEnv:
         self.num_players = self.info.num_players
         self.legal_bytes = self.info.legal_bytes
         self.action_dtype = torch.uint8 if self.info.action_bytes == 1 else torch.int16
-        L = _abi.lib()
-        h = C.c_void_p()
-        _abi.check(L.cs_create(C.byref(h), self.game, self.num_envs, self.device.index or 0, C.byref(self.cfg)),
-                   'cs_create')
-        self._h = h
+        self.create('cs_create', self.game, self.num_envs, self.device.index or 0, C.byref(self.cfg), out_first=True)
         if seeds is None:
             seeds = range(int(seed) + self.env_base, int(seed) + self.env_base + self.num_envs)
         self.seed(seeds)
 
-    # -- lifetime ----------------------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            _abi.lib().cs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
+    def _stream(self):   # (_abi.stream's body: one frame less on the per-step path)
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # -- API -----------------------------------------------------------------------------------------------------
     def seed(self, seeds, first_env=0):
         keys, lens = seed_keys(seeds)
         n = len(lens)
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_seed(self._h, keys.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p),
-                                          first_env, n, self._stream()), 'cs_seed')
+        _abi.call('cs_seed', self._h, keys.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), first_env, n,
+                  self._stream(), device=self.device)
 
     def new_step_out(self, lead=()):
         n, d = self.num_envs, self.device
@@ -113,8 +95,7 @@ class VecEnv:
 
     def reset(self, out=None):
         o = out if out is not None else self.new_step_out()
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_reset(self._h, C.byref(self._step_struct(o)), self._stream()), 'cs_reset')
+        _abi.call('cs_reset', self._h, C.byref(self._step_struct(o)), self._stream(), device=self.device)
         return o
 
     def step(self, actions, out=None):
@@ -122,17 +103,13 @@ class VecEnv:
         if a.numel() != self.num_envs:
             raise ValueError('expected %d actions, got %d' % (self.num_envs, a.numel()))
         o = out if out is not None else self.new_step_out()
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_step(self._h, _ptr(a), C.byref(self._step_struct(o)), self._stream()),
-                       'cs_step')
+        _abi.call('cs_step', self._h, _ptr(a), C.byref(self._step_struct(o)), self._stream(), device=self.device)
         return o
 
     def observe(self, player, out=None):
         o = out if out is not None else self.new_step_out()
         o = {k: o[k] for k in ('obs', 'legal', 'player', 'done')}
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_observe(self._h, int(player), C.byref(self._step_struct(o)), self._stream()),
-                       'cs_observe')
+        _abi.call('cs_observe', self._h, int(player), C.byref(self._step_struct(o)), self._stream(), device=self.device)
         return o
 
     # trajectory candidates new_traj_out allocates and ranks by default (placement): where a trajectory lands
@@ -153,26 +130,23 @@ class VecEnv:
 
     def state_bytes(self):
         """bytes of the envs' whole engine state (include/cardsim.h cs_state_bytes), 0 on a library without it"""
-        L = _abi.lib()
-        if not hasattr(L, 'cs_state_bytes'):
+        if not _abi.has('cs_state_bytes'):
             return 0
         n = C.c_int64()
-        _abi.check(L.cs_state_bytes(self._h, C.byref(n)), 'cs_state_bytes')
+        _abi.call('cs_state_bytes', self._h, C.byref(n))
         return n.value
 
     def save_state(self, buf=None):
         """the envs' whole engine state into a device buffer (cs_state_save; async on the env's stream) -> the buffer"""
         if buf is None:
             buf = torch.empty(self.state_bytes(), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_state_save(self._h, _ptr(buf), self._stream()), 'cs_state_save')
+        _abi.call('cs_state_save', self._h, _ptr(buf), self._stream(), device=self.device)
         return buf
 
     def load_state(self, buf):
         """the envs' whole engine state back from save_state's buffer (cs_state_load): rollouts, steps and resets
         since the save are undone"""
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_state_load(self._h, _ptr(buf), self._stream()), 'cs_state_load')
+        _abi.call('cs_state_load', self._h, _ptr(buf), self._stream(), device=self.device)
 
     def new_traj_out(self, T, final_obs=False, select=None, rank='rollout'):
         """Trajectory buffers [T, N, ...] for rollout(). The placement is chosen: up to `select` candidates (default
@@ -254,12 +228,11 @@ class VecEnv:
         """ms of one placement probe (include/cardsim.h cs_traj_probe: the rollout's writes, zeros, no state change)
         over the trajectory `traj`, timed with events on the env's stream."""
         T = int(T if T is not None else traj['player'].shape[0])
-        s = _abi.TrajOut(_ptr(traj['obs']), _ptr(traj['legal']), _ptr(traj['player']), _ptr(traj['action']),
-                         _ptr(traj['reward']), _ptr(traj['done']), None)
+        s = _abi.traj(traj, 'obs', 'legal', 'player', 'action', 'reward', 'done')
         with torch.cuda.device(self.device):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _abi.check(_abi.lib().cs_traj_probe(self._h, T, C.byref(s), self._stream()), 'cs_traj_probe')
+            _abi.call('cs_traj_probe', self._h, T, C.byref(s), self._stream())
             e1.record()
             e1.synchronize()
         return e0.elapsed_time(e1)
@@ -272,27 +245,17 @@ class VecEnv:
         with policy_id (rlcard_amd.models) -- played on the device (cs_rollout_policy); random seats pick what the plain
         rollout picks. None: the plain rollout (cs_rollout)."""
         o = out if out is not None else self.new_traj_out(T, final_obs)
-        s = _abi.TrajOut(_ptr(o['obs']), _ptr(o['legal']), _ptr(o['player']), _ptr(o['action']),
-                         _ptr(o['reward']), _ptr(o['done']), _ptr(o.get('final_obs')))
+        s = _abi.traj(o)
         seed = int(policy_seed) & (2 ** 64 - 1)
-        with torch.cuda.device(self.device):
-            if policies is None:
-                _abi.check(_abi.lib().cs_rollout(self._h, int(T), seed, int(t0), self.env_base, C.byref(s),
-                                                 self._stream()), 'cs_rollout')
-            else:
-                seats = self._seat_policies(policies)
-                _abi.check(self._policy_fn('cs_rollout_policy')(self._h, int(T), seed, int(t0), self.env_base, seats,
-                                                                C.byref(s), self._stream()), 'cs_rollout_policy')
+        if policies is None:
+            _abi.call('cs_rollout', self._h, int(T), seed, int(t0), self.env_base, C.byref(s), self._stream(),
+                      device=self.device)
+        else:
+            _abi.call('cs_rollout_policy', self._h, int(T), seed, int(t0), self.env_base, self._seat_policies(policies),
+                      C.byref(s), self._stream(), device=self.device)
         return o
 
     # -- policies on the device (include/cardsim.h CS_POLICY_*) --------------------------------------------------------
-    @staticmethod
-    def _policy_fn(name):
-        L = _abi.lib()
-        if not hasattr(L, name):   # an older A/B build: an error, never a host fallback
-            raise _abi.CardsimError('%s lacks %s' % (_abi.LIB_PATH, name))
-        return getattr(L, name)
-
     def _seat_policies(self, policies):
         from .models import policy_id_of
         ids = [policy_id_of(p) for p in policies]
@@ -306,10 +269,8 @@ class VecEnv:
         starts the next game). 'random' picks what rollout(policies=...) picks at step counter t."""
         from .models import policy_id_of
         a = out if out is not None else torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _abi.check(self._policy_fn('cs_policy_actions')(self._h, policy_id_of(policy),
-                                                            int(policy_seed) & (2 ** 64 - 1), int(t), self.env_base,
-                                                            _ptr(a), self._stream()), 'cs_policy_actions')
+        _abi.call('cs_policy_actions', self._h, policy_id_of(policy), int(policy_seed) & (2 ** 64 - 1), int(t),
+                  self.env_base, _ptr(a), self._stream(), device=self.device)
         return a
 
     def new_payoff_sums(self):
@@ -324,11 +285,8 @@ class VecEnv:
         (cs_payoff_sums): env e contributes a game only while acc['games_per_env'][e] < quota (quota <= 0: always), so
         over consecutive windows every env contributes exactly its first `quota` games."""
         T = traj['done'].shape[0]
-        tr = _abi.TrajOut(None, None, None, None, _ptr(traj['reward']), _ptr(traj['done']), None)
-        with torch.cuda.device(self.device):
-            _abi.check(self._policy_fn('cs_payoff_sums')(self._h, int(T), C.byref(tr), int(quota),
-                                                         _ptr(acc['games_per_env']), _ptr(acc['sums']),
-                                                         _ptr(acc['games']), self._stream()), 'cs_payoff_sums')
+        _abi.call('cs_payoff_sums', self._h, int(T), C.byref(_abi.traj(traj, 'reward', 'done')), int(quota),
+                  _ptr(acc['games_per_env']), _ptr(acc['sums']), _ptr(acc['games']), self._stream(), device=self.device)
         return acc
 
     # -- after the rollout (SURVEY 8(f)) ----------------------------------------------------------------------------
@@ -342,11 +300,9 @@ class VecEnv:
                  reward=torch.empty((T, self.num_envs), dtype=torch.float32, device=d),
                  done=torch.empty((T, self.num_envs), dtype=torch.uint8, device=d),
                  ret=torch.empty((T, self.num_envs), dtype=torch.float32, device=d))
-        tr = _abi.TrajOut(None, None, _ptr(traj['player']), None, _ptr(traj['reward']), _ptr(traj['done']), None)
         so = _abi.TransOut(*(_ptr(o[k]) for k in ('next_t', 'end_t', 'reward', 'done', 'ret')))
-        with torch.cuda.device(self.device):
-            _abi.check(_abi.lib().cs_transitions(self._h, int(T), C.byref(tr), C.byref(so), self._stream()),
-                       'cs_transitions')
+        _abi.call('cs_transitions', self._h, int(T), C.byref(_abi.traj(traj, 'player', 'reward', 'done')), C.byref(so),
+                  self._stream(), device=self.device)
         return o
 
     def legal_lists(self, legal):
@@ -356,13 +312,12 @@ class VecEnv:
         R = rows.shape[0]
         counts = torch.empty(R, dtype=torch.int32, device=self.device)
         offsets = torch.empty(R + 1, dtype=torch.int64, device=self.device)
-        L, st = _abi.lib(), self._stream()
-        with torch.cuda.device(self.device):
-            _abi.check(L.cs_legal_lists(self._h, _ptr(rows), R, _ptr(counts), _ptr(offsets), None, st), 'cs_legal_lists')
-            total = int(offsets[-1].item())
-            ids = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
-            _abi.check(L.cs_legal_lists(self._h, _ptr(rows), R, _ptr(counts), _ptr(offsets), _ptr(ids), st),
-                       'cs_legal_lists')
+        st = self._stream()
+        _abi.call('cs_legal_lists', self._h, _ptr(rows), R, _ptr(counts), _ptr(offsets), None, st, device=self.device)
+        total = int(offsets[-1].item())
+        ids = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+        _abi.call('cs_legal_lists', self._h, _ptr(rows), R, _ptr(counts), _ptr(offsets), _ptr(ids), st,
+                  device=self.device)
         return counts, offsets, ids[:total]
 
     def action_features(self, ids):
@@ -370,20 +325,19 @@ class VecEnv:
         ids = torch.as_tensor(ids, device=self.device).to(torch.int32).contiguous().reshape(-1)
         out = torch.empty((ids.numel(), self.info.action_feature_dim), dtype=torch.uint8, device=self.device)
         if ids.numel():
-            with torch.cuda.device(self.device):
-                _abi.check(_abi.lib().cs_action_features(self._h, _ptr(ids), ids.numel(), _ptr(out), self._stream()),
-                           'cs_action_features')
+            _abi.call('cs_action_features', self._h, _ptr(ids), ids.numel(), _ptr(out), self._stream(),
+                      device=self.device)
         return out
 
     # -- introspection (synchronous) ------------------------------------------------------------------------------
     def env_state_words(self, env):
         buf = (C.c_uint32 * self.info.state_words)()
-        _abi.check(_abi.lib().cs_get_env_state(self._h, int(env), buf, self.info.state_words), 'cs_get_env_state')
+        _abi.call('cs_get_env_state', self._h, int(env), buf, self.info.state_words)
         return list(buf)
 
     def set_env_state_words(self, env, words):
         buf = (C.c_uint32 * self.info.state_words)(*[int(w) & 0xFFFFFFFF for w in words])
-        _abi.check(_abi.lib().cs_set_env_state(self._h, int(env), buf, self.info.state_words), 'cs_set_env_state')
+        _abi.call('cs_set_env_state', self._h, int(env), buf, self.info.state_words)
 
     @property
     def rng_period(self):
@@ -438,7 +392,7 @@ class VecEnv:
         do not count: they belong to the games after the current one (queue layout: include/cardsim.h,
         cs_get_env_state)."""
         v = C.c_uint32()
-        _abi.check(_abi.lib().cs_get_rng_ctl(self._h, int(env), C.byref(v)), 'cs_get_rng_ctl')
+        _abi.call('cs_get_rng_ctl', self._h, int(env), C.byref(v))
         pos = v.value & (0x7FF if self.env_id == 'doudizhu' else 0x3FFF)   # cs_ring.h ctl layout
         cap = self.info.deal_queue_depth
         if cap > 0:
@@ -453,7 +407,7 @@ class VecEnv:
         return pos % self.rng_period
 
     def set_kernel_flags(self, flags):
-        _abi.check(_abi.lib().cs_debug_set_kernel_flags(self._h, int(flags)), 'cs_debug_set_kernel_flags')
+        _abi.call('cs_debug_set_kernel_flags', self._h, int(flags))
 
     def set_serial_refill(self, enable):
-        _abi.check(_abi.lib().cs_debug_set_serial_refill(self._h, 1 if enable else 0), 'cs_debug_set_serial_refill')
+        _abi.call('cs_debug_set_serial_refill', self._h, 1 if enable else 0)

@@ -47,20 +47,24 @@ def ref_act(traj, P, T, feature):
 
 @pytest.mark.parametrize('game,n,T_roll,launches,Tc', [('leduc-holdem', 300, 64, 6, 20), ('blackjack', 200, 32, 5, 10),
                                                        ('doudizhu', 40, 32, 8, 25), ('limit-holdem', 150, 48, 5, 30),
-                                                       ('no-limit-holdem', 100, 40, 4, 16)])
+                                                       ('no-limit-holdem', 100, 40, 4, 16),
+                                                       # windows of unequal length on one handle (two waves plus two
+                                                       # envs): the fill scratch grows, then is reused at a smaller size
+                                                       ('leduc-holdem', 130, (2, 8, 2), 3, 5)])
 def test_actor_buffers_match_reference_act_loop(game, n, T_roll, launches, Tc):
     from rlcard_amd import VecEnv
     from rlcard_amd.agents.dmc_agent import ActorBuffers, shapes_of
     v = VecEnv(game, n, seed=11)
     v.reset()
-    buf = ActorBuffers(v, T=Tc, slots=3 + (T_roll + Tc - 1) // Tc)
+    windows = T_roll if isinstance(T_roll, tuple) else (T_roll,) * launches
+    buf = ActorBuffers(v, T=Tc, slots=3 + (max(windows) + Tc - 1) // Tc)
     P = v.num_players
     feats = v.action_features(torch.arange(v.num_actions, device=v.device)).cpu().numpy().astype(np.int8)
     state_shape, _ = shapes_of(v)
     got = {}
     rows = []
-    for c in range(launches):
-        tr = v.rollout(T_roll, policy_seed=4, t0=c * T_roll)
+    for c, T in enumerate(windows):
+        tr = v.rollout(T, policy_seed=4, t0=sum(windows[:c]))
         rows.append({k: x.cpu().numpy() for k, x in tr.items()})
         ready = buf.fill(tr)
         ready_np = ready.cpu().numpy()

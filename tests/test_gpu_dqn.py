@@ -267,37 +267,43 @@ def assert_same(got, want, what):
         assert np.array_equal(got[k], want[k]), (what, k)
 
 
-REPLAY_CASES = [('leduc-holdem', None, 300), ('no-limit-holdem', None, 100), ('blackjack', None, 200),
-                ('leduc-holdem', {'game_num_players': 3}, 96)]
+# (game, config, envs, steps of each window, capacities: everything held; wraps; a longest-window push overflows it)
+EQUAL_WINDOWS = ((16,) * 5, (1 << 16, 1000, 64))
+REPLAY_CASES = [('leduc-holdem', None, 300) + EQUAL_WINDOWS, ('no-limit-holdem', None, 100) + EQUAL_WINDOWS,
+                ('blackjack', None, 200) + EQUAL_WINDOWS, ('leduc-holdem', {'game_num_players': 3}, 96) + EQUAL_WINDOWS,
+                # two waves plus two envs; the push scratch grows (2 -> 8 steps) and is reused at a smaller size
+                ('leduc-holdem', None, 130, (2, 8, 2), (1 << 16, 200, 97))]
 
 
 @pytest.mark.parametrize('all_seats', [False, True], ids=['seat0', 'all'])
-@pytest.mark.parametrize('case', REPLAY_CASES, ids=['leduc', 'nolimit', 'blackjack', 'leduc3'])
+@pytest.mark.parametrize('case', REPLAY_CASES, ids=['leduc', 'nolimit', 'blackjack', 'leduc3', 'leduc-grow'])
 def test_replay_matches_reorganize_with_carry(case, all_seats):
     from rlcard_amd import VecEnv
     from rlcard_amd.agents import DeviceMemory
-    game, config, n = case
+    game, config, n, windows, caps = case
     v = VecEnv(game, n, seed=21, config=config)
     v.reset()
     seats = tuple(range(v.num_players)) if all_seats else (0,)
-    caps = (1 << 16, 1000, 64)      # everything held; wraps; a single push overflows it
     mems = [DeviceMemory(v, cap) for cap in caps]
     ref = RefReplay(v.num_players, v.obs_dim, v.legal_bytes)
-    tr = v.new_traj_out(16, final_obs=True, select=1)
-    carried = 0
-    for w in range(5):
-        v.rollout(16, policy_seed=3, t0=16 * w, out=tr)
+    trajs = {T: v.new_traj_out(T, final_obs=True, select=1) for T in set(windows)}
+    carried = t0 = 0
+    for w, T in enumerate(windows):
+        tr = trajs[T]
+        v.rollout(T, policy_seed=3, t0=t0, out=tr)
+        t0 += T
         for mem in mems:
             mem.push(tr, seats)
         before = len(ref.out)
         ref.push({k: x.cpu().numpy() for k, x in tr.items()}, seats)
         carried += len(ref.pending)
-        assert len(ref.out) - before > 64       # every push overflows the smallest ring
+        if T == max(windows):
+            assert len(ref.out) - before > caps[2]       # the push overflows the smallest ring
         for mem, cap in zip(mems, caps):
             assert mem.sizes() == (min(len(ref.out), cap), len(ref.out))
-        assert_same(held(mems[2]), ref.held(64), 'capacity 64 after push %d' % w)
+        assert_same(held(mems[2]), ref.held(caps[2]), 'capacity %d after push %d' % (caps[2], w))
     assert carried > 0
-    assert len(ref.out) > 1000
+    assert len(ref.out) > caps[1]
     for mem, cap in zip(mems, caps):
         assert_same(held(mem), ref.held(cap), 'capacity %d' % cap)
     want = ref.held(1 << 16)
@@ -348,6 +354,26 @@ def test_replay_straddling_transition_once_and_drop_pending():
         s, a = pend[key]
         assert np.array_equal(got['state'][first + j], s.astype(np.float32)) and got['action'][first + j] == a
     assert_same(held(drop), ref_drop.held(1 << 14), 'dropped')
+
+
+def test_buffers_may_be_closed_after_their_env():
+    """include/cardsim.h: a buffer may be destroyed after its handle. Closing the env first, then its three kinds of
+    buffer, raises nothing and leaves the device usable."""
+    from rlcard_amd import VecEnv
+    from rlcard_amd.agents import DeviceMemory
+    from rlcard_amd.agents.dmc_agent import ActorBuffers
+    from rlcard_amd.agents.nfsp_agent import DeviceReservoir
+    v = VecEnv('leduc-holdem', 64, seed=4)
+    bufs = [DeviceMemory(v, 256), DeviceReservoir(v, 256, seed=1), ActorBuffers(v, T=4, slots=3)]
+    v.close()
+    for b in bufs:
+        b.close()
+        assert b._h is None
+    fresh = VecEnv('leduc-holdem', 64, seed=4)
+    fresh.reset()
+    out = fresh.step(fresh.policy_actions('random'))
+    torch.cuda.synchronize()
+    assert out['obs'].shape == (64, fresh.obs_dim) and int(out['obs'].sum()) > 0
 
 
 # ---- targets ----------------------------------------------------------------------------------------------------------

@@ -402,30 +402,38 @@ def assert_same_reservoir(res, ref, A, what):
     assert np.array_equal(pr.argmax(axis=1), np.array([d[1] for d in ref.data])), what
 
 
-RESERVOIR_CASES = [('leduc-holdem', None, 300), ('leduc-holdem', {'game_num_players': 3}, 96)]
+# (game, config, envs, steps of each window, a capacity smaller than the longest window's push, and a number of
+# candidates every push exceeds)
+RESERVOIR_CASES = [('leduc-holdem', None, 300, (16,) * 5, 64, 100),
+                   ('leduc-holdem', {'game_num_players': 3}, 96, (16,) * 5, 64, 100),
+                   # two waves plus two envs; the push scratch grows (2 -> 8 steps) and is reused at a smaller size. A
+                   # 2-step window has 260 rows, a quarter of them seat 0's in best-response mode: 30 is far below that
+                   ('leduc-holdem', None, 130, (2, 8, 2), 97, 30)]
 
 
 @pytest.mark.parametrize('all_seats', [False, True], ids=['seat0', 'all'])
-@pytest.mark.parametrize('case', RESERVOIR_CASES, ids=['leduc', 'leduc3'])
+@pytest.mark.parametrize('case', RESERVOIR_CASES, ids=['leduc', 'leduc3', 'leduc-grow'])
 def test_reservoir_matches_sequential_add(case, all_seats):
     from rlcard_amd import VecEnv
     from rlcard_amd.agents import DeviceReservoir
-    game, config, n = case
+    game, config, n, steps, small, least = case
     v = VecEnv(game, n, seed=21, config=config)
     v.reset()
     P, A = v.num_players, v.num_actions
     seats = tuple(range(P)) if all_seats else (0,)
     g = torch.Generator().manual_seed(6)
     windows = []
-    for w in range(5):
-        tr = v.rollout(16, policy_seed=3, t0=16 * w, final_obs=True)
+    t0 = 0
+    for T in steps:
+        tr = v.rollout(T, policy_seed=3, t0=t0, final_obs=True)
+        t0 += T
         tr = {k: x.clone() for k, x in tr.items()}
-        mode = (torch.rand((16, n), generator=g) < 0.5).to(torch.uint8).to(v.device)
+        mode = (torch.rand((T, n), generator=g) < 0.5).to(torch.uint8).to(v.device)
         windows.append((tr, mode, {k: x.cpu().numpy() for k, x in tr.items()}, mode.cpu().numpy()))
     counts = [len(RefReservoir(1, 0, P).candidates(wh, mh, seats)) for _, _, wh, mh in windows]
-    assert min(counts) > 100
+    assert min(counts) > least and max(counts) > small
     mid = counts[0] + counts[1] + counts[2] // 2         # fills in the middle of the third push
-    caps = (1 << 16, mid, 64)
+    caps = (1 << 16, mid, small)
     seed = 2 ** 40 + 9
     res = [DeviceReservoir(v, cap, seed) for cap in caps]
     refs = [RefReservoir(cap, seed, P) for cap in caps]
@@ -450,7 +458,7 @@ def test_reservoir_matches_sequential_add(case, all_seats):
     # clear empties it, and the stream starts again
     res[2].clear()
     assert res[2].sizes() == (0, 0)
-    fresh = RefReservoir(64, seed, P)
+    fresh = RefReservoir(small, seed, P)
     tr, mode, wh, mh = windows[0]
     res[2].push(tr, mode, seats)
     fresh.push(wh, mh, seats)

@@ -1,8 +1,8 @@
 // san_driver.cpp -- AddressSanitizer + UndefinedBehaviorSanitizer run over the host-side C/C++: the CPU
 // oracle (oracle/*.c, every game through create / seed / reset / step / observe / rollout, CFR, the evaluator and the
 // DouDizhu legal-set KAT hook), the C ABI's host code (include/cardsim.h entry points on their argument-validation and
-// no-device paths; cs_abi.cpp) and the DouDizhu table expansion (cs_ddz_table.cpp table_build_host). Built by
-// `make -C tools san_driver` with -fsanitize=address,undefined on those sources only (the HIP kernels are linked
+// no-device paths; cs_abi.cpp), the carver of the agents' buffer layouts (cs_devbuf.h) and the DouDizhu table
+// expansion (cs_ddz_table.cpp table_build_host). Built by `make -C tools san_driver` with -fsanitize=address,undefined on those sources only (the HIP kernels are linked
 // unsanitized: GPU sanitizers are not available here). Test infrastructure; run by tests/test_sanitizers.py.
 // Exit 0 = every check passed and no sanitizer report (reports abort: -fno-sanitize-recover).
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include <vector>
 #include "../include/cardsim.h"
 #include "../oracle/oracle.h"
+#include "../rlcard_amd/csrc/cs_devbuf.h"
 #include "../rlcard_amd/csrc/cs_doudizhu.h"
 
 namespace cs {
@@ -202,6 +203,116 @@ static void abi_host()
     cs_destroy(nullptr);
 }
 
+// the agents' entry points (DMC, DQN, NFSP) on the paths that run without a GPU: null handles and outputs, ranges
+static void abi_host_agents()
+{
+    cs_dmc* d = nullptr;
+    cs_replay* rp = nullptr;
+    cs_reservoir* rv = nullptr;
+    int64_t i64 = 0;
+    uint32_t u32 = 0;
+    float f = 0.f;
+    int32_t i32 = 0;
+    uint8_t u8 = 0;
+    cs_traj_out traj;
+    memset(&traj, 0, sizeof(traj));
+    cs_qnet net;
+    memset(&net, 0, sizeof(net));
+    EXPECT(cs_dmc_create(nullptr, 4, 2, &d) == CS_E_INVALID && d == nullptr);
+    EXPECT(cs_dmc_fill(nullptr, 1, &traj, &i64, 1, &i64, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dmc_gather(nullptr, 0, &i64, 1, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dmc_status(nullptr, &u32) == CS_E_INVALID);
+    EXPECT(cs_dmc_layer1(nullptr, &f, &i32, &i32, 1, 4, &f, &f, &f, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dmc_select(nullptr, &i32, &i64, &i32, 1, 0.f, 0, 0, 0, &i32, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dmc_select(&f, &i32, &i64, &i32, 1, 0.f, 0, 0, 0, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dmc_select(&f, &i32, &i64, &i32, 0, 0.f, 0, 0, 0, &i32, nullptr) == CS_E_INVALID);
+    EXPECT(strcmp(cs_last_error(), "S must be positive") == 0);
+    cs_dmc_destroy(nullptr);
+
+    EXPECT(cs_qnet_values(nullptr, &net, &u8, &u8, 1, &f, nullptr) == CS_E_INVALID);
+    EXPECT(cs_qnet_actions(nullptr, &net, &u8, &u8, &u8, 1, 0.f, 0, 0, 0, &i32, &f, nullptr) == CS_E_INVALID);
+    EXPECT(cs_replay_create(nullptr, 8, &rp) == CS_E_INVALID && rp == nullptr);
+    EXPECT(cs_replay_push(nullptr, 1, &traj, 1u, nullptr) == CS_E_INVALID);
+    EXPECT(cs_replay_drop_pending(nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_replay_size(nullptr, &i64, &i64) == CS_E_INVALID);
+    EXPECT(cs_replay_gather(nullptr, &i64, 1, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(nullptr, &f, &u8, &f, &u8, 1, 4, 0.9f, &f, &i32, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, 1, 4, 0.9f, nullptr, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(&f, nullptr, &u8, &f, &u8, 1, 4, 0.9f, &f, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, 1, 0, 0.9f, &f, &i32, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, -1, 4, 0.9f, &f, &i32, nullptr) == CS_E_INVALID);
+    EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, 0, 4, 0.9f, &f, &i32, nullptr) == CS_OK);
+    cs_replay_destroy(nullptr);
+
+    EXPECT(cs_pnet_probs(nullptr, &net, &u8, &u8, 1, &f, nullptr) == CS_E_INVALID);
+    EXPECT(cs_nfsp_scratch_bytes(-1) == CS_E_INVALID);
+    EXPECT(strcmp(cs_last_error(), "rows out of range") == 0);
+    EXPECT(cs_nfsp_scratch_bytes((int64_t)1 << 31) == CS_E_INVALID);
+    EXPECT(cs_nfsp_actions(nullptr, &net, &net, &u8, &u8, &u8, &u8, 1, 0.f, 0, 0, 0, &i32, &f, &u8, nullptr) ==
+           CS_E_INVALID);
+    EXPECT(cs_reservoir_create(nullptr, 8, 0, &rv) == CS_E_INVALID && rv == nullptr);
+    EXPECT(cs_reservoir_push(nullptr, 1, &traj, &u8, 1u, nullptr) == CS_E_INVALID);
+    EXPECT(cs_reservoir_size(nullptr, &i64, &i64) == CS_E_INVALID);
+    EXPECT(cs_reservoir_gather(nullptr, &i64, 1, &f, &f, nullptr) == CS_E_INVALID);
+    EXPECT(cs_reservoir_clear(nullptr, nullptr) == CS_E_INVALID);
+    cs_reservoir_destroy(nullptr);
+}
+
+// cs::Carve on the part sequences of cs_dmc_create, cs_replay_create and cs_reservoir_create: every part's offset and
+// the total, as literals (the layouts these buffers have always had: each part padded to a multiple of 256 bytes)
+template <size_t N>
+static void expect_offsets(const size_t (&got)[N], const size_t (&want)[N])
+{
+    for (size_t k = 0; k < N; k++) EXPECT(got[k] == want[k]);
+}
+
+static void carve_dmc(size_t O, size_t F, size_t n, size_t P, size_t slots, size_t T, const size_t (&want)[12])
+{
+    const size_t streams = n * P, rows = streams * slots * T;
+    cs::Carve c;
+    const size_t got[12] = {c.take<int8_t>(rows * O), c.take<int8_t>(rows * F), c.take<float>(rows),
+                            c.take<float>(rows), c.take<uint8_t>(rows), c.take<int64_t>(streams),
+                            c.take<int64_t>(streams), c.take<int64_t>(streams), c.take<int32_t>(streams + 1),
+                            c.take<int64_t>(streams + 1), c.take<uint32_t>(1), c.bytes()};
+    expect_offsets(got, want);
+}
+
+static void carve_replay(size_t O, size_t LB, size_t P, size_t n, size_t cap, const size_t (&want)[12])
+{
+    const size_t NP = n * P;
+    cs::Carve c;
+    const size_t got[12] = {c.take<uint8_t>(cap * O), c.take<uint8_t>(cap * O), c.take<uint8_t>(cap * LB),
+                            c.take<int32_t>(cap), c.take<float>(cap), c.take<uint8_t>(cap), c.take<uint8_t>(NP * O),
+                            c.take<int32_t>(NP), c.take<int32_t>(NP), c.take<uint8_t>(NP), c.take<int64_t>(1),
+                            c.bytes()};
+    expect_offsets(got, want);
+}
+
+static void carve_reservoir(size_t O, size_t cap, const size_t (&want)[5])
+{
+    cs::Carve c;
+    const size_t got[5] = {c.take<uint8_t>(cap * O), c.take<int32_t>(cap), c.take<unsigned long long>(cap),
+                           c.take<int64_t>(1), c.bytes()};
+    expect_offsets(got, want);
+}
+
+static void carve_layouts()
+{
+    // Leduc (O 36, F 4), 130 envs x 2 players, 4 slots of 5 rows; DouDizhu (O 901, F 54), 5 envs x 3, 3 slots of 7
+    carve_dmc(36, 4, 130, 2, 4, 5,
+              {0, 187392, 208384, 229376, 250368, 255744, 258048, 260352, 262656, 263936, 266240, 266496});
+    carve_dmc(901, 54, 5, 3, 3, 7,
+              {0, 283904, 301056, 302336, 303616, 304128, 304384, 304640, 304896, 305152, 305408, 305664});
+    carve_replay(36, 1, 2, 130, 97, {0, 3584, 7168, 7424, 7936, 8448, 8704, 18176, 19456, 20736, 21248, 21504});
+    carve_replay(901, 16, 3, 5, 1000,
+                 {0, 901120, 1802240, 1818368, 1822464, 1826560, 1827584, 1841152, 1841408, 1841664, 1841920, 1842176});
+    carve_reservoir(36, 97, {0, 3584, 4096, 5120, 5376});         // (cs_reservoir_clear's tail: 5376 - 4096)
+    carve_reservoir(901, 1000, {0, 901120, 905216, 913408, 913664});
+    cs::DevBuf b;   // an empty buffer: nothing to free, nothing asked of the device
+    EXPECT(b.reserve(0) == hipSuccess && b.p == nullptr && b.bytes == 0);
+    b.release();
+}
+
 int main()
 {
     std::vector<uint8_t> host;
@@ -212,6 +323,8 @@ int main()
     EXPECT(err.empty());
     EXPECT(tab.ng == 308 && tab.rocket > 0 && tab.bomb_hi > tab.bomb_lo);
     abi_host();
+    abi_host_agents();
+    carve_layouts();
     if (!err.empty()) return 1;
     oracle_ddz_table(host, off);
     oracle_games();
