@@ -28,14 +28,16 @@ enum {
     CS_E_UNSUPPORTED = -4
 };
 
-/* game ids; names as registered by rlcard/envs/__init__.py:6-54 */
-enum { CS_GAME_BLACKJACK = 0, CS_GAME_LEDUC = 1, CS_GAME_LIMIT = 2, CS_GAME_DOUDIZHU = 3, CS_GAME_NOLIMIT = 4 };
+/* game ids; names as registered by rlcard/envs/__init__.py:6-54 (CS_GAME_UNO: 'uno', two players) */
+enum { CS_GAME_BLACKJACK = 0, CS_GAME_LEDUC = 1, CS_GAME_LIMIT = 2, CS_GAME_DOUDIZHU = 3, CS_GAME_NOLIMIT = 4,
+       CS_GAME_UNO = 5 };
 
 typedef struct cs_handle cs_handle;
 
 /* Game configuration: the 'game_*' keys Env.__init__ forwards to Game.configure (rlcard/envs/env.py:33-39). */
 typedef struct {
-    int32_t num_players; /* blackjack 'game_num_players' (default 1); leduc/limit/no-limit 2; doudizhu 3 (0 = default) */
+    int32_t num_players; /* blackjack 'game_num_players' (default 1); leduc/limit/no-limit 2; doudizhu 3 (0 = default);
+                            uno 2 only: any other count is CS_E_UNSUPPORTED (the reference's payoffs[1 - winner]) */
     int32_t num_decks;   /* blackjack 'game_num_decks' (default 1, 0 = infinite); ignored elsewhere (-1 = default) */
     int32_t chips_for_each; /* no-limit 'chips_for_each' (nolimitholdem/game.py:45-56): stack, 1..255 (0 = 100) */
     int32_t dealer_plus1;   /* no-limit 'dealer_id' + 1: 0 = None (drawn by the first game, then kept), 1..N fixed */
@@ -50,8 +52,9 @@ enum { CS_RNG_MT19937 = 0, CS_RNG_PHILOX = 1 };
 
 /* Static shape of a game (rlcard Env.num_players / num_actions / state_shape). */
 typedef struct {
-    int32_t obs_dim;      /* bytes per obs row: leduc 36, limit 72, no-limit 54, blackjack 2, doudizhu 901 (landlord 790) */
-    int32_t num_actions;  /* leduc/limit 4, no-limit 5, blackjack 2, doudizhu 27472 */
+    int32_t obs_dim;      /* bytes per obs row: leduc 36, limit 72, no-limit 54, blackjack 2, doudizhu 901 (landlord 790),
+                             uno 240 ([4][4][15] row-major, every row holds exactly 61 ones) */
+    int32_t num_actions;  /* leduc/limit 4, no-limit 5, blackjack 2, doudizhu 27472, uno 61 (8 legal bytes) */
     int32_t num_players;
     int32_t legal_bytes;  /* ceil(num_actions / 8): legal-action bitmask bytes per row */
     int32_t action_bytes; /* dtype width of rollout action rows: 1 (uint8) or 2 (int16, doudizhu) */
@@ -144,7 +147,10 @@ int cs_seed(cs_handle* h, const uint32_t* keys, const int32_t* key_len, int64_t 
 int cs_reset(cs_handle* h, const cs_step_out* out, void* stream);
 
 /* One Env.step (envs/env.py:65-86) per env with actions [n] int32 (DEVICE memory). Illegal ids follow the
- * reference's _decode_action (envs/leducholdem.py:81-96, limitholdem.py:81-96). Envs whose game was already over
+ * reference's _decode_action (envs/leducholdem.py:81-96, limitholdem.py:81-96); where the reference is undefined the
+ * ABI defines the step -- UNO: an illegal id plays the lowest legal id (the reference draws a legal id from the global
+ * np.random), and a deal or draw that finds fewer cards than it needs even after replace_deck takes the cards that are
+ * there (the reference raises IndexError). Envs whose game was already over
  * start a new game instead (lazy auto-reset: action ignored, done = 0, reward = 0), so an RL loop never calls
  * reset() per env. */
 int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* stream);
@@ -166,10 +172,16 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
  *   CS_POLICY_RANDOM   uniform over the legal actions, the policy of cs_rollout (same Philox counter, same pick)
  *   CS_POLICY_RULE_V1  Leduc: leduc-holdem-rule-v1 (raise, else call, else check, else fold);
  *                      Limit: limit-holdem-rule-v1 (hole-card classes against the board's ranks and suits)
+ *                      UNO: uno-rule-v1 (rlcard/models/uno_rule_models.py): `draw` if legal; else, with a wild_draw_4
+ *                      legal, the wild_draw_4 of the colour most frequent in the hand (wild cards left out unless the
+ *                      hand is all wild, ties to the colour met first in hand order); else uniform over the legal ids
+ *                      without the *-wild ids (kept if nothing else is legal) -- the reference draws that pick from the
+ *                      global np.random, the engine from the step's policy word with CS_POLICY_RANDOM's formula, so a
+ *                      rule seat's games are a function of policy_seed
  *   CS_POLICY_RULE_V2  Leduc only: leduc-holdem-rule-v2 (raise on a rank match with the public card, else fold)
- * A rule that aims at an illegal action plays call for raise, fold for check and raise for call, as the reference does.
- * Rule policies exist for default 2-player Leduc and heads-up Limit hold'em; with any other game or player count a
- * rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit). */
+ * A hold'em rule that aims at an illegal action plays call for raise, fold for check and raise for call, as the reference
+ * does. Rule policies exist for default 2-player Leduc, heads-up Limit hold'em and UNO; with any other game or player
+ * count a rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit and on UNO). */
 enum { CS_POLICY_RANDOM = 0, CS_POLICY_RULE_V1 = 1, CS_POLICY_RULE_V2 = 2 };
 
 /* cs_rollout with seat p playing seat_policy[p] (HOST array of num_players CS_POLICY_* ids): the way to play a fixed

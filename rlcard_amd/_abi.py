@@ -10,7 +10,15 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get('CARDSIM_LIB', 'libcardsim.so'))   # CARDSIM_LIB: A/B builds only
 
+# the games with a restatement under oracle/ (bench.py's games; tests/test_abi.py records cs_game_info for exactly these)
 GAME_IDS = {'blackjack': 0, 'leduc-holdem': 1, 'limit-holdem': 2, 'doudizhu': 3, 'no-limit-holdem': 4}
+# games pinned by the reference's recorded streams alone
+RECORDED_GAME_IDS = {'uno': 5}
+
+
+def game_id(env_id):
+    """env id -> CS_GAME_* (include/cardsim.h), None for an id the engine does not have"""
+    return GAME_IDS.get(env_id, RECORDED_GAME_IDS.get(env_id))
 
 CS_OK = 0
 _ERRORS = {-1: 'CS_E_INVALID', -2: 'CS_E_DEVICE', -3: 'CS_E_STATE', -4: 'CS_E_UNSUPPORTED'}
@@ -234,5 +242,5 @@ def game_info(game, num_players=0, num_decks=-1, chips_for_each=0, dealer_id=Non
     cfg = Config(num_players, num_decks, chips_for_each, 0 if dealer_id is None else int(dealer_id) + 1,
                  RNG_MODES[rng_mode])
     info = GameInfo()
-    call('cs_game_info_get', GAME_IDS[game] if isinstance(game, str) else game, C.byref(cfg), C.byref(info))
+    call('cs_game_info_get', game_id(game) if isinstance(game, str) else game, C.byref(cfg), C.byref(info))
     return info, cfg

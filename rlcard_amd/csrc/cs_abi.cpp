@@ -121,6 +121,8 @@ int cs_game_info_get(int32_t game, const cs_config* cfg, cs_game_info* info)
     if (!info) return fail(CS_E_INVALID, "info is null");
     memset(info, 0, sizeof(*info));
     const cs::GameOps* ops = cs::find_game(game, cfg);
+    if (!ops && game == CS_GAME_UNO)
+        return fail(CS_E_UNSUPPORTED, "uno: game_num_players must be 2 (the reference's payoffs are defined for two)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     *info = ops->info;
     return CS_OK;
@@ -134,6 +136,8 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     if (cfg && cfg->rng_mode != CS_RNG_MT19937 && cfg->rng_mode != CS_RNG_PHILOX)
         return fail(CS_E_INVALID, "rng_mode must be CS_RNG_MT19937 or CS_RNG_PHILOX");
     const cs::GameOps* ops = cs::find_game(game, cfg);
+    if (!ops && game == CS_GAME_UNO)
+        return fail(CS_E_UNSUPPORTED, "uno: game_num_players must be 2 (the reference's payoffs are defined for two)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     const cs_game_info& info = ops->info;
     int ndev = 0;
@@ -319,7 +323,7 @@ int cs_rollout_policy(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0
         uint32_t seats = 0;
         for (int32_t p = 0; p < P; p++) {
             if (!h->ops->rollout_policy || seat_policy[p] > h->ops->max_policy)
-                return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2) and limit-holdem (v1) only");
+                return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2), limit-holdem (v1) and uno (v1) only");
             seats |= (uint32_t)seat_policy[p] << (8 * p);   // (P = 2 wherever rollout_policy is set)
         }
         e = h->ops->rollout_policy(h->b, T, policy_seed, t0, env_base, seats, *out, (hipStream_t)stream);
@@ -333,7 +337,7 @@ int cs_policy_actions(cs_handle* h, int32_t policy, uint64_t policy_seed, uint64
     if (!h || !actions) return fail(CS_E_INVALID, "null argument");
     if (policy < CS_POLICY_RANDOM || policy > CS_POLICY_RULE_V2) return fail(CS_E_INVALID, "unknown policy id");
     if (!h->ops->policy_actions || policy > h->ops->max_policy)
-        return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2) and limit-holdem (v1) only");
+        return fail(CS_E_UNSUPPORTED, "rule policies: 2-player leduc-holdem (v1, v2), limit-holdem (v1) and uno (v1) only");
     if (!h->seeded) return fail(CS_E_STATE, "cs_policy_actions before cs_seed");
     int r = set_device(h);
     if (r != CS_OK) return r;

@@ -57,6 +57,9 @@ struct GameDefaults {
     static constexpr int SPARSE_K = 0;     // > 0: obs rows are one-hot with SPARSE_K known positions (observe_pos)
     static constexpr int MAX_POLICY = 0;   // > 0: the largest CS_POLICY_* id of the game's rule_action
     static constexpr int DQ = 0;           // > 0: deals drawn ahead into a queue of this depth (cs_dq.h)
+    // obs rows stored by their own lane, 16 B at a time, instead of through the wave's LDS span image: for games whose
+    // occupancy is bound by LDS and whose rows are 16-B multiples (UNO: the 60 KB image per block was one block per CU)
+    static constexpr bool OBS_DIRECT = false;
 };
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
@@ -275,6 +278,15 @@ __device__ __forceinline__ int pick_legal32(uint32_t legal, uint32_t r)
     int k = (int)__umulhi(r, (uint32_t)count);
     while (k--) legal &= legal - 1;
     return __builtin_ctz(legal);
+}
+// the same pick over a <= 64-action legal mask (UNO's 61 ids)
+__device__ __forceinline__ int pick_legal64(uint64_t legal, uint32_t r)
+{
+    const int count = __popcll(legal);
+    if (count == 0) return -1;
+    int k = (int)__umulhi(r, (uint32_t)count);
+    while (k--) legal &= legal - 1;
+    return __builtin_ctzll(legal);
 }
 // the same pick for masks of at most A bits (A <= 8), branch-free: the k-th set bit after k clears of the lowest
 // (k < A), so a wave's lanes never loop to the largest k among them

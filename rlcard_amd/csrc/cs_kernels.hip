@@ -10,6 +10,7 @@
 #include "cs_blackjack.h"
 #include "cs_doudizhu.h"
 #include "cs_nolimit.h"
+#include "cs_uno.h"
 
 namespace cs {
 
@@ -63,6 +64,7 @@ const GameOps* find_game(int32_t game, const cs_config* cfg)
         if (p > 2) return find_holdem_n(game, p);
         return p == 2 ? ops_of<Nolimit>() : nullptr;
     }
+    case CS_GAME_UNO: return (np == 0 || np == Uno::P) ? ops_of<Uno>() : nullptr;   // (cs_create names the refusal)
     case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
     default: return nullptr;
     }

@@ -59,12 +59,38 @@ __device__ __forceinline__ void refill(M& m, int lane, int flags)
     if (!(flags & 1)) ring_refill_wave(m, lane);
 }
 
+// one 0/1 obs row from its bitmap as nontemporal 16-B stores by its own lane (G::OBS_DIRECT; rows are 16-B multiples,
+// so a 16-B aligned tensor makes every store aligned; emit_obs falls back to dword stores for any other)
+template <class G>
+__device__ __forceinline__ void write_obs_rows16(uint8_t* o, const uint32_t (&bits)[G::NB])
+{
+    static_assert(!G::RAW_OBS && G::OBS % 16 == 0, "direct rows: 0/1 bytes, a 16-B multiple per row");
+#pragma unroll
+    for (int q = 0; q < G::OBS / 16; q++) {
+        uint4 v;
+        v.x = RowWriter<G::OBS>::expand4(bits[(4 * q) / 8] >> (4 * ((4 * q) % 8)));
+        v.y = RowWriter<G::OBS>::expand4(bits[(4 * q + 1) / 8] >> (4 * ((4 * q + 1) % 8)));
+        v.z = RowWriter<G::OBS>::expand4(bits[(4 * q + 2) / 8] >> (4 * ((4 * q + 2) % 8)));
+        v.w = RowWriter<G::OBS>::expand4(bits[(4 * q + 3) / 8] >> (4 * ((4 * q + 3) % 8)));
+        out_store16((uint4*)o + q, v);
+    }
+}
+
+template <class G>
+__device__ __forceinline__ void write_obs_direct(uint8_t* o, const uint32_t (&bits)[G::NB]);   // (below)
+
 // obs rows: staged + coalesced when the row is a dword multiple, per-lane bytes otherwise
 template <class G, int ROWS = WAVE>
 __device__ __forceinline__ void emit_obs(uint32_t* lds, const uint32_t (&bits)[G::NB], uint8_t* obs, int64_t row0, int flags,
                                          const LaneCtx& c)
 {
-    if constexpr (G::RAW_OBS && G::OBS % 2 == 0) {
+    if constexpr (G::OBS_DIRECT) {
+        if (c.valid) {   // (the row stride is a 16-B multiple: the tensor's alignment is every row's)
+            uint8_t* o = obs + (row0 + c.lane) * G::OBS;
+            if ((((uintptr_t)o) & 15u) == 0) write_obs_rows16<G>(o, bits);
+            else write_obs_direct<G>(o, bits);
+        }
+    } else if constexpr (G::RAW_OBS && G::OBS % 2 == 0) {
         RowWriterRaw<G::OBS, ROWS>::write(lds, bits, obs + row0 * G::OBS, c.lane, c.nvalid, !(flags & 4));
     } else if constexpr (G::RAW_OBS) {
         if (c.valid) {
@@ -124,7 +150,8 @@ __device__ __forceinline__ void emit_reward(float* reward, int64_t row, const fl
 template <class G, int ROWS>
 constexpr int obs_lds_words()
 {
-    if constexpr (!G::RAW_OBS && G::OBS % 4 == 0) return RowWriter<G::OBS, ROWS>::LDS_WORDS;
+    if constexpr (G::OBS_DIRECT) return 1;
+    else if constexpr (!G::RAW_OBS && G::OBS % 4 == 0) return RowWriter<G::OBS, ROWS>::LDS_WORDS;
     else if constexpr (G::RAW_OBS && G::OBS % 2 == 0) return RowWriterRaw<G::OBS, ROWS>::LDS_WORDS;
     else return 1;
 }
@@ -442,15 +469,18 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
         // slower on every torch allocation, profiles/EXPERIMENTS.md)
         const uint32_t pr = pol.at(seed, genv0, t0 + (uint64_t)t, t == 0);
         int a;
-        static_assert(G::A <= 32, "the policy pick takes a 32-bit legal mask");
+        static_assert(G::A <= 64, "the policy pick takes a 64-bit legal mask");
         if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
-        else a = pick_legal32((uint32_t)lg, pr);
+        else if constexpr (G::A <= 32) a = pick_legal32((uint32_t)lg, pr);
+        else a = pick_legal64(lg, pr);
         if constexpr (POL) {
             // the seats' policies are one word of the argument block (a scalar load); the acting seat's byte picks
             // between the random pick above -- always made, at cs_rollout's counter, so random seats play the same
             // games -- and the rule's answer on the state in registers. A rule seat draws nothing.
             const uint32_t pid = (A.seats >> (8 * p)) & 0xFFu;
-            const int ra = g.rule_action(pid, p, (uint32_t)lg);
+            int ra;
+            if constexpr (G::A <= 32) ra = g.rule_action(pid, p, (uint32_t)lg);
+            else ra = g.rule_action(pid, p, lg, pr);   // wide games' rules may pick at random: the step's policy word
             a = pid == (uint32_t)CS_POLICY_RANDOM ? a : ra;
         }
 #if !CS_PROF_NO_OBS
@@ -536,16 +566,28 @@ __global__ __launch_bounds__(BLOCK) void k_policy_actions(const uint32_t* st, in
                                                            GameParams prm)
 {
     const int64_t env = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t* lane_scratch = nullptr;
+    if constexpr (G::SCRATCH_WORDS > 0) {   // games whose state lives in LDS (one env per thread, like lane_ctx)
+        __shared__ uint32_t scr[WAVES_PER_BLOCK][Scratch<G>::WORDS];
+        lane_scratch = scratch_of<G>(scr[threadIdx.x / WAVE], threadIdx.x & (WAVE - 1));
+    }
     if (env >= n) return;
     G g;
-    g.bind(nullptr, prm);
+    g.bind(lane_scratch, prm);
     g.blank();
     g.load(st, n, env);
     int a = -1;
     if (!g.is_over()) {
-        const uint32_t lg = (uint32_t)g.legal();
-        if (policy == CS_POLICY_RANDOM) a = pick_legal_small<G::A>(lg, philox_u32(seed, env_base + (uint64_t)env, t));
-        else a = g.rule_action((uint32_t)policy, g.current(), lg);
+        if constexpr (G::A <= 32) {
+            const uint32_t lg = (uint32_t)g.legal();
+            if (policy == CS_POLICY_RANDOM) a = pick_legal_small<G::A>(lg, philox_u32(seed, env_base + (uint64_t)env, t));
+            else a = g.rule_action((uint32_t)policy, g.current(), lg);
+        } else {
+            const uint64_t lg = g.legal();
+            const uint32_t pr = philox_u32(seed, env_base + (uint64_t)env, t);
+            if (policy == CS_POLICY_RANDOM) a = pick_legal64(lg, pr);
+            else a = g.rule_action((uint32_t)policy, g.current(), lg, pr);
+        }
     }
     actions[env] = a;
 }

@@ -1,5 +1,5 @@
 """The env registry: rlcard's plugin API (rlcard/envs/registration.py:8-89, envs/__init__.py) -- register(env_id,
-'module:Class') and make(env_id, config) -- over the engine's five games. Same ids, same config defaults and the same
+'module:Class') and make(env_id, config) -- over the engine's six games. Same ids, same config defaults and the same
 ValueError messages for an unknown or a duplicate id."""
 import importlib
 
@@ -33,3 +33,4 @@ register('leduc-holdem', 'rlcard_amd.envs.leducholdem:LeducholdemEnv')
 register('limit-holdem', 'rlcard_amd.envs.limitholdem:LimitholdemEnv')
 register('doudizhu', 'rlcard_amd.envs.doudizhu:DoudizhuEnv')
 register('no-limit-holdem', 'rlcard_amd.envs.nolimitholdem:NolimitholdemEnv')
+register('uno', 'rlcard_amd.envs.uno:UnoEnv')

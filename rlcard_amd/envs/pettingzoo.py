@@ -105,5 +105,5 @@ class AECEnv(object):
 
 def env(env_id, config=None):
     """The AEC env of an engine game id ('leduc-holdem', 'limit-holdem', 'no-limit-holdem', 'doudizhu',
-    'blackjack')."""
+    'blackjack', 'uno')."""
     return AECEnv(env_id, config)

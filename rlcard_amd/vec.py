@@ -45,9 +45,9 @@ class VecEnv(_abi.Handle):
     def __init__(self, env_id, num_envs, seed=0, seeds=None, device=None, config=None, env_base=0):
         config = dict(config or {})
         self.env_id = env_id
-        if env_id not in _abi.GAME_IDS:
+        self.game = _abi.game_id(env_id)
+        if self.game is None:
             raise ValueError('Cannot find env_id: {}'.format(env_id))
-        self.game = _abi.GAME_IDS[env_id]
         self.num_envs = int(num_envs)
         self.env_base = int(env_base)
         if device is None:
@@ -56,6 +56,8 @@ class VecEnv(_abi.Handle):
         if self.device.type != 'cuda':
             raise _abi.CardsimError('VecEnv runs on the GPU only (got device %s)' % self.device)
         np_ = int(config.get('game_num_players', 0))
+        if env_id == 'uno' and np_ not in (0, 2):   # the engine answers CS_E_UNSUPPORTED (include/cardsim.h)
+            raise ValueError('uno: game_num_players must be 2, got %d' % np_)
         nd = int(config.get('game_num_decks', -1))
         chips = int(config.get('chips_for_each', 0))
         self.rng_mode = config.get('rng_mode', 'mt19937')   # 'philox': fast, not the reference's deals
