@@ -318,18 +318,20 @@ typedef struct {
     int32_t in_dim;        /* = cs_game_info.obs_dim */
     int32_t num_hidden;    /* 1..4 tanh layers */
     int32_t hidden[4];     /* widths, each 1..128 */
-    int32_t num_actions;   /* = cs_game_info.num_actions, <= 8 */
+    int32_t num_actions;   /* = cs_game_info.num_actions, <= 64 */
     int32_t reserved;
     const float* W[5];     /* W[k] [out_k][in_k] row-major (torch Linear.weight), W[num_hidden] = output layer */
     const float* b[5];
 } cs_qnet;
 
 /* DQNAgent.predict for `rows` observation rows: obs u8 [rows][obs_dim], legal u8 [rows][legal_bytes] or NULL (every
- * action legal) -> q f32 [rows][num_actions], -inf where the action is illegal. Refusals (both functions): a game with
- * more than 8 actions CS_E_UNSUPPORTED (DouDizhu), so is a net whose activations need more than 64 KB of LDS per 64 rows
- * (max(in_dim, hidden[1], hidden[3]) + max(hidden[0], hidden[2]) above 256: two 128-wide layers are the largest);
- * in_dim / num_actions not the handle's game's, widths or layer counts out of range, null weights
- * CS_E_INVALID. */
+ * action legal) -> q f32 [rows][num_actions], -inf where the action is illegal. The mask is the row's legal_bytes
+ * bytes read as one little-endian word (UNO: 8 bytes, 61 bits); bits from num_actions up are ignored. Refusals (both
+ * functions): a game with more than 64 actions CS_E_UNSUPPORTED (DouDizhu); in_dim / num_actions not the handle's
+ * game's, widths or layer counts out of range, null weights CS_E_INVALID. Every descriptor within those ranges runs on
+ * every game of at most 64 actions there is (a block of 64 rows needs 74 240 B of LDS at most: a game of more than 8
+ * actions or 128 obs bytes keeps its obs rows as bytes); a net that needed more than the 160 KiB a block can have --
+ * only a game with some 1 700 obs bytes could -- would be CS_E_UNSUPPORTED. */
 int cs_qnet_values(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* q,
                    void* stream);
 /* DQNAgent.step / eval_step for `rows` rows: actions i32 [rows] = the first maximum of the row's Q-values among its
@@ -405,7 +407,7 @@ int cs_nfsp_actions(cs_handle* h, const cs_qnet* qnet, const cs_qnet* pnet, cons
 
 /* Reservoir buffer of a handle's envs on the device (nfsp_agent.py ReservoirBuffer of (info_state, action_probs)).
  * Only best-response steps are stored and their action_probs are one-hot, so a slot holds state u8 [obs_dim] and the
- * action id. Games with more than 8 actions (DouDizhu) are CS_E_UNSUPPORTED. */
+ * action id. Games with more than 64 actions (DouDizhu) are CS_E_UNSUPPORTED. */
 typedef struct cs_reservoir cs_reservoir;
 int  cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reservoir** out);
 void cs_reservoir_destroy(cs_reservoir* r);

@@ -45,16 +45,23 @@ def descriptor(wb, device):
     return net
 
 
-def fold_batchnorm(bn, linears):
+def fold_batchnorm(bn, linears, weights32=False):
     """[(W, b)] per Linear as float64 numpy, the eval-mode BatchNorm1d `bn` folded into the first: with s = gamma /
     sqrt(running_var + eps) and c = beta - running_mean * s, BatchNorm is x * s + c, so W0' = W0 * s (per input
-    column) and b0' = b0 + W0 . c."""
+    column) and b0' = b0 + W0 . c. weights32 (the device descriptors): the running mean's share of b0' is taken with W0'
+    as float32 will hold it, b0' = b0 + W0 . beta - fl32(W0') . running_mean, so that the kernel's sum is fl32(W0') .
+    (x - running_mean) + ...: a weight's rounding then counts by how far its feature is from its mean, not by the
+    feature (a trained UNO net has scales s of up to 316 on features that hardly ever leave their mean)."""
     f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)   # noqa: E731
     s = f64(bn.weight) / np.sqrt(f64(bn.running_var) + bn.eps)
     c = f64(bn.bias) - f64(bn.running_mean) * s
     out = [(f64(m.weight), f64(m.bias)) for m in linears]
     W0, b0 = out[0]
-    out[0] = (W0 * s[None, :], b0 + W0 @ c)
+    Wf = W0 * s[None, :]
+    if weights32:
+        out[0] = (Wf, b0 + W0 @ f64(bn.bias) - Wf.astype(np.float32).astype(np.float64) @ f64(bn.running_mean))
+    else:
+        out[0] = (Wf, b0 + W0 @ c)
     return out
 
 
@@ -137,12 +144,15 @@ class Estimator:
 
     def folded(self):
         """The cs_qnet descriptor (_abi.QNet) of this network: folded_weights() as float32 tensors on the estimator's
-        device (kept alive by the descriptor's `tensors`). Cached; update(), load_state_dict() and any in-place change
-        of the parameters invalidate it."""
+        device (kept alive by the descriptor's `tensors`), the first bias folded around those float32 weights
+        (fold_batchnorm's weights32). Cached; update(), load_state_dict() and any in-place change of the parameters
+        invalidate it."""
         ver = self._version()
         if self._folded is not None and self._folded[0] == ver:
             return self._folded[1]
-        net = descriptor(self.folded_weights(), self.device)
+        net = descriptor(fold_batchnorm(self.qnet.fc_layers[1],
+                                        [m for m in self.qnet.fc_layers if isinstance(m, nn.Linear)], weights32=True),
+                         self.device)
         self._folded = (ver, net)
         return net
 

@@ -67,12 +67,14 @@ class AveragePolicyNetwork(nn.Module):
 
     def folded(self):
         """The cs_qnet descriptor (_abi.QNet) of this network, which cs_pnet_probs and cs_nfsp_actions read as
-        Linear/ReLU: folded_weights() as float32 tensors on the network's device. Cached; train_sl(),
+        Linear/ReLU: folded_weights() as float32 tensors on the network's device (the first bias folded around those
+        float32 weights, fold_batchnorm's weights32). Cached; train_sl(),
         load_state_dict() and any in-place change of the parameters invalidate it."""
         ver = self._version()
         if self._folded is not None and self._folded[0] == ver:
             return self._folded[1]
-        net = descriptor(self.folded_weights(), self.mlp[1].weight.device)
+        net = descriptor(fold_batchnorm(self.mlp[1], [m for m in self.mlp if isinstance(m, nn.Linear)], weights32=True),
+                         self.mlp[1].weight.device)
         self._folded = (ver, net)
         return net
 

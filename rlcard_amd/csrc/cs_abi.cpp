@@ -454,7 +454,7 @@ static int qnet_check(const cs_handle* h, const cs_qnet* net, const void* obs, i
 {
     if (!h || !net || !obs) return fail(CS_E_INVALID, "null argument");
     const cs_game_info& info = h->ops->info;
-    if (info.num_actions > 8) return fail(CS_E_UNSUPPORTED, "the Q-network kernel takes games of at most 8 actions");
+    if (info.num_actions > 64) return fail(CS_E_UNSUPPORTED, "the Q-network kernel takes games of at most 64 actions");
     if (net->in_dim != info.obs_dim || net->num_actions != info.num_actions)
         return fail(CS_E_INVALID, "cs_qnet: in_dim / num_actions are not the handle's game's");
     if (net->num_hidden < 1 || net->num_hidden > CS_QNET_MAX_HIDDEN)
@@ -464,8 +464,10 @@ static int qnet_check(const cs_handle* h, const cs_qnet* net, const void* obs, i
             return fail(CS_E_INVALID, "cs_qnet: hidden widths must be 1..128");
         if (!net->W[l] || !net->b[l]) return fail(CS_E_INVALID, "cs_qnet: null weights");
     }
-    if (cs::qnet_lds_bytes(*net) > 65536 + 2 * 4352)   // (64 KB of activations: two 128-wide layers, and two weight tiles)
-        return fail(CS_E_UNSUPPORTED, "cs_qnet: the net's activations need more than 64 KB of LDS per 64 rows");
+    // (every descriptor the checks above pass needs 74 240 B at most on the games there are: two 128-unit buffers and
+    // two weight tiles, the obs of a wide game being bytes inside the first buffer; this guards a future game's obs)
+    if (cs::qnet_lds_bytes(*net) > 160 * 1024)
+        return fail(CS_E_UNSUPPORTED, "cs_qnet: the net needs more than the 160 KiB of LDS a block can have");
     if (rows < 0 || rows > 0x7FFFFFFF) return fail(CS_E_INVALID, "rows out of range");
     return CS_OK;
 }
@@ -646,7 +648,7 @@ int cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reserv
     *out = nullptr;
     if (capacity <= 0) return fail(CS_E_INVALID, "capacity must be positive");
     const cs_game_info& info = h->ops->info;
-    if (info.num_actions > 8) return fail(CS_E_UNSUPPORTED, "cs_reservoir: games of at most 8 actions");
+    if (info.num_actions > 64) return fail(CS_E_UNSUPPORTED, "cs_reservoir: games of at most 64 actions");
     int rc = set_device(h);
     if (rc != CS_OK) return rc;
     const int64_t O = info.obs_dim, cap = capacity;

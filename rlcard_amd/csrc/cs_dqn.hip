@@ -16,6 +16,11 @@
 //                       registers while the previous stage's FMAs run. A net with a layer wider than 64 units runs two
 //                       waves per block, one per tile of the layer. The output layer (<= 8 actions) is one pass with a
 //                       lane per row, its weights staged once, and stays in registers for the mask and the argmax.
+//                       A game of 9..64 actions (UNO: 61, 240 obs bytes) takes the WIDE instantiations: the obs rows
+//                       stay the bytes they are, transposed [unit][row] (8 rows of a unit are one 8-B read, converted
+//                       in the first layer's loop), in the buffer that layer 1's outputs take over afterwards;
+//                       the output layer is one more 64 x 64 tile through the same loop without an activation, and
+//                       the head reads its row's column of that tile from LDS.
 //                     The same kernel is NFSP's average-policy network (rlcard/agents/nfsp_agent.py): a template on the
 //                     hidden activation (tanh | ReLU), the head (masked argmax + epsilon draw | softmax, remove_illegal
 //                     and a sampled action) and an optional row list; the tiling and the staging are shared.
@@ -34,7 +39,10 @@
 
 namespace cs {
 
-constexpr int QOC = 8;        // the most actions k_qnet takes: the output layer is one register pass of 8 units
+constexpr int QOC = 8;        // the most actions of the narrow head: its output layer is one register pass of 8 units
+constexpr int QWIDE = 64;     // the most actions of the wide head: its output layer is one more tile of 64 units
+constexpr int QBS = 72;       // bytes per input unit in the wide obs image: 64 rows + 8 (8-B aligned units; the staging
+                              // lanes' byte writes, four units apart, spread over 8 banks where 64 B would give one)
 constexpr int QROWS = 64;     // rows per block of k_qnet: one wave, or two that split a layer's 64-unit tiles
 constexpr int QKT = 16;       // input units per staged weight tile
 constexpr int QWS = 68;       // floats per input unit in the weight tile: 64 output units + 4 (16-B aligned rows whose
@@ -68,7 +76,112 @@ __device__ __forceinline__ float qnet_act(float x)
     else return tanhf(x);
 }
 
-template <int ACT, int HEAD, bool LIST>
+// The head of a game of up to 64 actions, run by wave 0 with a lane per row on the output tile col[a * 64 + lane]: the
+// narrow head's semantics (below) with the mask a 64-bit word of (A + 7) / 8 bytes per row, bits >= A ignored. img is
+// the other activation buffer, free by now: without a row list the block's q / probs rows are laid out there as
+// [row][A], the 64 A contiguous floats of the output, and stored by consecutive lanes; a listed row is its own segment.
+template <int HEAD, bool LIST>
+__device__ __forceinline__ void qnet_head_wide(float* xo, float* img, int A, const uint8_t* __restrict__ legal,
+                                               const uint8_t* __restrict__ done, int64_t rows, int64_t row0, int lane,
+                                               float eps, uint64_t seed, uint64_t t, uint64_t row_base,
+                                               int32_t* __restrict__ actions, float* __restrict__ q,
+                                               const int32_t* __restrict__ idx)
+{
+    const int64_t row = row0 + lane;
+    const bool live = row < rows;
+    int64_t orow = row;
+    if constexpr (LIST) orow = live ? idx[row] : 0;
+    const int LB = (A + 7) >> 3;
+    const uint64_t all = A >= 64 ? ~0ull : (1ull << A) - 1ull;
+    uint64_t mask = all;
+    if (legal && live) {
+        mask = 0;
+        for (int b = 0; b < LB; b++) mask |= (uint64_t)legal[orow * LB + b] << (8 * b);
+        mask &= all;
+    }
+    float* col = xo + lane;
+    float* mine = img + lane * A;
+    int pick = -1;
+    if constexpr (HEAD == Q_SOFTMAX) {
+        // the narrow head's chain in id order, the probabilities kept in the row's column between the passes
+        float mx = col[0];
+        for (int a = 1; a < A; a++) mx = fmaxf(mx, col[a * QROWS]);
+        float sum = 0.f;
+        for (int a = 0; a < A; a++) {
+            const float p = expf(col[a * QROWS] - mx);
+            col[a * QROWS] = p;
+            sum += p;
+        }
+        float lsum = 0.f;
+        for (int a = 0; a < A; a++) {
+            const float p = (mask >> a) & 1ull ? col[a * QROWS] / sum : 0.f;
+            col[a * QROWS] = p;
+            lsum += p;
+        }
+        const float uni = 1.0f / (float)__popcll(mask);
+        uint32_t r[4] = {0, 0, 0, 0};
+        if (actions) philox4(seed, row_base + (uint64_t)orow, t, r);
+        const float u = (float)(r[2] >> 8) * (1.0f / 16777216.0f);
+        int last = -1;
+        float c = 0.f;
+        for (int a = 0; a < A; a++) {
+            const bool lg = (mask >> a) & 1ull;
+            const float p = lg ? (lsum == 0.f ? uni : col[a * QROWS] / lsum) : 0.f;
+            if (q) {
+                if constexpr (LIST) {
+                    if (live) q[orow * A + a] = p;
+                } else mine[a] = p;
+            }
+            if (lg) {
+                c = c + p;
+                last = a;
+                if (pick < 0 && u < c) pick = a;
+            }
+        }
+        if (pick < 0) pick = last;   // (rounding left the sum below u)
+    } else {
+        float bv = 0.f;
+        for (int a = 0; a < A; a++) {
+            const bool lg = (mask >> a) & 1ull;
+            const float v = col[a * QROWS];
+            if (lg && (pick < 0 || v > bv)) {
+                pick = a;
+                bv = v;
+            }
+            if (q) {
+                if constexpr (LIST) {
+                    if (live) q[orow * A + a] = lg ? v : -INFINITY;
+                } else mine[a] = lg ? v : -INFINITY;
+            }
+        }
+        if (actions && pick >= 0 && eps > 0.f) {   // k_dmc_select's draw (cs_dmc.hip)
+            uint32_t r[4];
+            philox4(seed, row_base + (uint64_t)orow, t, r);
+            const float u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+            if (u < eps) {
+                int kth = (int)(((uint64_t)r[1] * (uint64_t)__popcll(mask)) >> 32);
+                uint64_t m = mask;
+                while (kth-- > 0) m &= m - 1;
+                pick = __builtin_ctzll(m);
+            }
+        }
+    }
+    if constexpr (!LIST) {
+        if (q) {   // (the wave's own LDS writes, read back in program order)
+            __builtin_amdgcn_wave_barrier();
+            const int64_t left = rows - row0;
+            const int n = (int)(left < QROWS ? left : QROWS) * A;
+            float* dst = q + row0 * A;
+            for (int e = lane; e < n; e += QROWS) dst[e] = img[e];
+        }
+    }
+    if (!actions || !live) return;
+    if (done && done[orow]) pick = -1;
+    actions[orow] = pick;
+}
+
+// WIDE: a game of more than 8 actions or more than 128 obs bytes -- the byte obs image and the wide head.
+template <int ACT, int HEAD, bool LIST, bool WIDE = false>
 __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, int szB, const uint8_t* __restrict__ obs,
                                                 const uint8_t* __restrict__ legal, const uint8_t* __restrict__ done,
                                                 int64_t rows, float eps, uint64_t seed, uint64_t t, uint64_t row_base,
@@ -89,7 +202,33 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
     float* bufB = bufA + szA * QROWS;     // [szB][64]: the outputs of layers 0, 2
     float* wt0 = bufB + szB * QROWS;      // [NW][QKT][QWS]: a weight tile per wave, input-unit major
     float* wt = wt0 + wv * QWT;
-    {   // obs rows of the block -> bufA as floats: consecutive lanes, consecutive bytes
+    if constexpr (WIDE) {
+        // obs rows of the block -> bufA as the bytes they are, [unit][QBS] (qnet_sizes counts them into szA; layer 1
+        // overwrites them once layer 0 has read them). Consecutive lanes take consecutive dwords of the block's rows
+        // (bytes where the rows are not dword-aligned), (row, unit) stepped along without a division per element.
+        uint8_t* xb = (uint8_t*)bufA;
+        const int64_t left = rows - row0;
+        const int nr = (int)(left < QROWS ? left : QROWS);
+        const int G = (((D & 3) | (int)((uintptr_t)obs & 3)) == 0) ? 4 : 1, DG = D / G;
+        const int dr = BT / DG, du = BT - dr * DG;
+        int r = tid / DG, u = tid - r * DG;
+        while (r < nr) {
+            int64_t srow = row0 + r;
+            if constexpr (LIST) srow = idx[srow];
+            const uint8_t* src = obs + srow * D + u * G;
+            if (G == 4) {
+                const uint32_t w = *(const uint32_t*)src;
+#pragma unroll
+                for (int i = 0; i < 4; i++) xb[(u * 4 + i) * QBS + r] = (uint8_t)(w >> (8 * i));
+            } else xb[u * QBS + r] = *src;
+            r += dr;
+            u += du;
+            if (u >= DG) {
+                u -= DG;
+                r++;
+            }
+        }
+    } else {   // obs rows of the block -> bufA as floats: consecutive lanes, consecutive bytes
         const int64_t left = rows - row0;
         const int nb = (int)(left < QROWS ? left : QROWS) * D;
         const uint8_t* src = obs + row0 * D;
@@ -103,8 +242,10 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
     float* xin = bufA;
     float* xout = bufB;
     int in = D;
-    for (int l = 0; l < NH; l++) {
-        const int out = net.hidden[l];
+    // (wide: the output layer is one more pass of the loop, a tile of A units -- the staging gives units A.. zero
+    // weights, and they are not stored -- without an activation, [action][row] into the free buffer)
+    for (int l = 0; l < (WIDE ? NH + 1 : NH); l++) {
+        const int out = WIDE && l == NH ? A : net.hidden[l];
         const float* __restrict__ W = net.W[l];
         const float* __restrict__ bias = net.b[l];
         for (int ot0 = 0; ot0 < out; ot0 += 64 * NW) {   // (every wave passes the barriers; one without a tile idles)
@@ -133,6 +274,24 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
                 if (!mine) continue;
                 if (kt + QKT < in) qnet_tile_load(W, in, out, ot, kt + QKT, lane, pre);   // in flight under the FMAs
                 const int kn = in - kt < QKT ? in - kt : QKT;
+                if (WIDE && l == 0) {   // the obs bytes: 8 rows of a unit are one 8-B read
+#pragma unroll 2
+                    for (int k = 0; k < kn; k++) {
+                        const uint2 x = *(const uint2*)((const uint8_t*)xin + (kt + k) * QBS + lr * 8);
+                        const float4 w0 = *(const float4*)(wt + k * QWS + lo * 8);
+                        const float4 w1 = *(const float4*)(wt + k * QWS + lo * 8 + 4);
+                        const float a[8] = {(float)(x.x & 255u), (float)((x.x >> 8) & 255u),
+                                            (float)((x.x >> 16) & 255u), (float)(x.x >> 24),
+                                            (float)(x.y & 255u), (float)((x.y >> 8) & 255u),
+                                            (float)((x.y >> 16) & 255u), (float)(x.y >> 24)};
+                        const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+                        for (int j = 0; j < 8; j++)
+#pragma unroll
+                            for (int i = 0; i < 8; i++) acc[j][i] = fmaf(w[j], a[i], acc[j][i]);
+                    }
+                    continue;
+                }
 #pragma unroll 2
                 for (int k = 0; k < kn; k++) {
                     const float4 a0 = *(const float4*)(xin + (kt + k) * QROWS + lr * 8);
@@ -147,11 +306,17 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
                         for (int i = 0; i < 8; i++) acc[j][i] = fmaf(w[j], a[i], acc[j][i]);
                 }
             }
+            const bool act = !(WIDE && l == NH);
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int o = ot + lo * 8 + j;
                 if (o < out) {
                     float* d = xout + o * QROWS + lr * 8;
+                    if (!act) {
+                        *(float4*)d = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+                        *(float4*)(d + 4) = make_float4(acc[j][4], acc[j][5], acc[j][6], acc[j][7]);
+                        continue;
+                    }
                     *(float4*)d = make_float4(qnet_act<ACT>(acc[j][0]), qnet_act<ACT>(acc[j][1]),
                                               qnet_act<ACT>(acc[j][2]), qnet_act<ACT>(acc[j][3]));
                     *(float4*)(d + 4) = make_float4(qnet_act<ACT>(acc[j][4]), qnet_act<ACT>(acc[j][5]),
@@ -163,6 +328,12 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
         xin = xout;
         xout = nx;
         in = out;
+    }
+    if constexpr (WIDE) {   // wave 0, a lane per row, on its column of the output tile (xin after the last swap)
+        __syncthreads();
+        if (wv != 0) return;
+        qnet_head_wide<HEAD, LIST>(xin, xout, A, legal, done, rows, row0, lane, eps, seed, t, row_base, actions, q, idx);
+        return;
     }
     // output layer, one lane per row: its weights as wt[k][8] (zeros past A), read back as two broadcast float4
     __syncthreads();
@@ -266,12 +437,22 @@ __global__ __launch_bounds__(2 * QROWS) void k_qnet(const cs_qnet net, int szA, 
     }
 }
 
+// the wide instantiations: more actions than the narrow head's register pass, or more obs units than fit as floats
+static bool qnet_wide(const cs_qnet& net) { return net.num_actions > QOC || net.in_dim > 128; }
+
+// units ([64] floats each) of the two activation buffers. Wide: the output tile lands in one of them and the head's
+// [row][A] image of q / probs in the other, so each holds 64 units at least, and bufA the obs bytes ([in_dim][QBS])
 static void qnet_sizes(const cs_qnet& net, int* szA, int* szB)
 {
-    int a = net.in_dim, b = 1;
+    const bool wide = qnet_wide(net);
+    int a = wide ? QWIDE : net.in_dim, b = wide ? QWIDE : 1;
     for (int l = 0; l < net.num_hidden; l++) {
         int& dst = (l & 1) ? a : b;
         if (net.hidden[l] > dst) dst = net.hidden[l];
+    }
+    if (wide) {
+        const int ob = (net.in_dim * QBS + QROWS * 4 - 1) / (QROWS * 4);
+        if (ob > a) a = ob;
     }
     *szA = a;
     *szB = b;
@@ -300,7 +481,7 @@ static hipError_t launch_net(const cs_qnet& net, const uint8_t* obs, const uint8
     int szA, szB;
     qnet_sizes(net, &szA, &szB);
     const int64_t bytes = qnet_lds_bytes(net);
-    auto kern = k_qnet<ACT, HEAD, LIST>;
+    auto kern = qnet_wide(net) ? k_qnet<ACT, HEAD, LIST, true> : k_qnet<ACT, HEAD, LIST, false>;
     if (bytes > 65536) {   // past the default limit of dynamic LDS (the [128, 128, ..] nets): raise this kernel's
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
@@ -598,6 +779,8 @@ __global__ __launch_bounds__(QBLOCK) void k_dqn_targets(const float* __restrict_
                                                         const uint8_t* __restrict__ done, int64_t B, int A, int LB,
                                                         float gamma, float* target, int32_t* best)
 {
+#pragma clang fp contract(off)   // the product and the sum below round separately (__fmul_rn / __fadd_rn are plain
+                                 // operators in the headers' scope: under the default contraction the two fused)
     const int64_t i = (int64_t)blockIdx.x * QBLOCK + threadIdx.x;
     if (i >= B) return;
     int bi = -1;
@@ -613,7 +796,10 @@ __global__ __launch_bounds__(QBLOCK) void k_dqn_targets(const float* __restrict_
     }
     if (bi < 0) bi = 0;
     if (best) best[i] = bi;
-    if (target) target[i] = __fadd_rn(reward[i], __fmul_rn(done[i] ? 0.f : gamma, qt[i * A + bi]));
+    if (target) {
+        const float prod = (done[i] ? 0.f : gamma) * qt[i * A + bi];
+        target[i] = reward[i] + prod;
+    }
 }
 
 hipError_t launch_dqn_targets(const float* q_next, const float* q_next_target, const uint8_t* next_legal,
