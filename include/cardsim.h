@@ -28,16 +28,18 @@ enum {
     CS_E_UNSUPPORTED = -4
 };
 
-/* game ids; names as registered by rlcard/envs/__init__.py:6-54 (CS_GAME_UNO: 'uno', two players) */
+/* game ids; names as registered by rlcard/envs/__init__.py:6-54 (CS_GAME_UNO: 'uno', two players; CS_GAME_MAHJONG:
+ * 'mahjong', four players) */
 enum { CS_GAME_BLACKJACK = 0, CS_GAME_LEDUC = 1, CS_GAME_LIMIT = 2, CS_GAME_DOUDIZHU = 3, CS_GAME_NOLIMIT = 4,
-       CS_GAME_UNO = 5 };
+       CS_GAME_UNO = 5, CS_GAME_MAHJONG = 6 };
 
 typedef struct cs_handle cs_handle;
 
 /* Game configuration: the 'game_*' keys Env.__init__ forwards to Game.configure (rlcard/envs/env.py:33-39). */
 typedef struct {
     int32_t num_players; /* blackjack 'game_num_players' (default 1); leduc/limit/no-limit 2; doudizhu 3 (0 = default);
-                            uno 2 only: any other count is CS_E_UNSUPPORTED (the reference's payoffs[1 - winner]) */
+                            uno 2 only: any other count is CS_E_UNSUPPORTED (the reference's payoffs[1 - winner]);
+                            mahjong 4 only: any other count is CS_E_UNSUPPORTED */
     int32_t num_decks;   /* blackjack 'game_num_decks' (default 1, 0 = infinite); ignored elsewhere (-1 = default) */
     int32_t chips_for_each; /* no-limit 'chips_for_each' (nolimitholdem/game.py:45-56): stack, 1..255 (0 = 100) */
     int32_t dealer_plus1;   /* no-limit 'dealer_id' + 1: 0 = None (drawn by the first game, then kept), 1..N fixed */
@@ -53,8 +55,10 @@ enum { CS_RNG_MT19937 = 0, CS_RNG_PHILOX = 1 };
 /* Static shape of a game (rlcard Env.num_players / num_actions / state_shape). */
 typedef struct {
     int32_t obs_dim;      /* bytes per obs row: leduc 36, limit 72, no-limit 54, blackjack 2, doudizhu 901 (landlord 790),
-                             uno 240 ([4][4][15] row-major, every row holds exactly 61 ones) */
-    int32_t num_actions;  /* leduc/limit 4, no-limit 5, blackjack 2, doudizhu 27472, uno 61 (8 legal bytes) */
+                             uno 240 ([4][4][15] row-major, every row holds exactly 61 ones), mahjong 816 ([6][34][4]
+                             row-major: hand, table, the four players' piles; a tile's row is 1 in columns < its count) */
+    int32_t num_actions;  /* leduc/limit 4, no-limit 5, blackjack 2, doudizhu 27472, uno 61 (8 legal bytes),
+                             mahjong 38 (5 legal bytes: tiles 0..33, pong 34, chow 35, gong 36, stand 37) */
     int32_t num_players;
     int32_t legal_bytes;  /* ceil(num_actions / 8): legal-action bitmask bytes per row */
     int32_t action_bytes; /* dtype width of rollout action rows: 1 (uint8) or 2 (int16, doudizhu) */
@@ -150,7 +154,9 @@ int cs_reset(cs_handle* h, const cs_step_out* out, void* stream);
  * reference's _decode_action (envs/leducholdem.py:81-96, limitholdem.py:81-96); where the reference is undefined the
  * ABI defines the step -- UNO: an illegal id plays the lowest legal id (the reference draws a legal id from the global
  * np.random), and a deal or draw that finds fewer cards than it needs even after replace_deck takes the cards that are
- * there (the reference raises IndexError). Envs whose game was already over
+ * there (the reference raises IndexError); Mahjong: an illegal id plays the lowest legal id (the reference raises),
+ * a game already won on the deal is done = 1 at the reset row with zero rewards, and a finished game's legal mask may
+ * be zero. Envs whose game was already over
  * start a new game instead (lazy auto-reset: action ignored, done = 0, reward = 0), so an RL loop never calls
  * reset() per env. */
 int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* stream);
@@ -181,7 +187,8 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
  *   CS_POLICY_RULE_V2  Leduc only: leduc-holdem-rule-v2 (raise on a rank match with the public card, else fold)
  * A hold'em rule that aims at an illegal action plays call for raise, fold for check and raise for call, as the reference
  * does. Rule policies exist for default 2-player Leduc, heads-up Limit hold'em and UNO; with any other game or player
- * count a rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit and on UNO). */
+ * count a rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit and on UNO, and every rule id on
+ * Mahjong, for which the reference has no rule model; cs_policy_actions(CS_POLICY_RANDOM) works there). */
 enum { CS_POLICY_RANDOM = 0, CS_POLICY_RULE_V1 = 1, CS_POLICY_RULE_V2 = 2 };
 
 /* cs_rollout with seat p playing seat_policy[p] (HOST array of num_players CS_POLICY_* ids): the way to play a fixed
@@ -483,6 +490,13 @@ int cs_get_rng_ctl(cs_handle* h, int64_t env, uint32_t* host_ctl);
  * S H D C x A 2 .. K; DEVICE), values uint32 [n] (DEVICE): category << 20 | five 4-bit tie-break ranks -- larger
  * wins, equal splits. No handle: the evaluator is stateless. */
 int cs_debug_holdem_rank7(const int8_t* cards, int64_t n, uint32_t* values, void* stream);
+
+/* Mahjong win-judge test hook: the judge_hu of the Mahjong kernels (rlcard/games/mahjong/judger.py judge_hu / cal_set)
+ * on `n` ordered hands: hands u8 [n][14] (tile = action id 0..33, in hand order -- the order decides which pairs the
+ * judge tries), len u8 [n] (tiles used of each row, <= 14), piles u8 [n] (the player's pile count) -> win u8 [n]
+ * (0 / 1). All DEVICE memory; stateless (no handle). */
+int cs_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n, uint8_t* win,
+                        void* stream);
 
 /* DouDizhu legal-set test hook: the legal-action bitmask the step / rollout kernels build, for `n` (hand, previous
  * play) cases: counts u8 [n][15] (cards per rank 3 .. A, 2, black joker, red joker), prev i32 [n] (the largest play

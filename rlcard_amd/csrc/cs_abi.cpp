@@ -123,6 +123,8 @@ int cs_game_info_get(int32_t game, const cs_config* cfg, cs_game_info* info)
     const cs::GameOps* ops = cs::find_game(game, cfg);
     if (!ops && game == CS_GAME_UNO)
         return fail(CS_E_UNSUPPORTED, "uno: game_num_players must be 2 (the reference's payoffs are defined for two)");
+    if (!ops && game == CS_GAME_MAHJONG)
+        return fail(CS_E_UNSUPPORTED, "mahjong: game_num_players must be 4 (the reference's game is four-handed)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     *info = ops->info;
     return CS_OK;
@@ -138,6 +140,8 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
     const cs::GameOps* ops = cs::find_game(game, cfg);
     if (!ops && game == CS_GAME_UNO)
         return fail(CS_E_UNSUPPORTED, "uno: game_num_players must be 2 (the reference's payoffs are defined for two)");
+    if (!ops && game == CS_GAME_MAHJONG)
+        return fail(CS_E_UNSUPPORTED, "mahjong: game_num_players must be 4 (the reference's game is four-handed)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     const cs_game_info& info = ops->info;
     int ndev = 0;
@@ -890,6 +894,14 @@ int cs_debug_holdem_rank7(const int8_t* cards, int64_t n, uint32_t* values, void
     if (!cards || !values) return fail(CS_E_INVALID, "null argument");
     if (n <= 0 || n > ((int64_t)1 << 31)) return fail(CS_E_INVALID, "n out of range");
     return done(cs::launch_debug_rank7(cards, n, values, (hipStream_t)stream), "cs_debug_holdem_rank7");
+}
+
+int cs_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n, uint8_t* win,
+                        void* stream)
+{
+    if (!hands || !len || !piles || !win) return fail(CS_E_INVALID, "null argument");
+    if (n <= 0 || n > ((int64_t)1 << 31)) return fail(CS_E_INVALID, "n out of range");
+    return done(cs::launch_debug_mahjong_hu(hands, len, piles, n, win, (hipStream_t)stream), "cs_debug_mahjong_hu");
 }
 
 int cs_debug_ddz_legal(cs_handle* h, const uint8_t* counts, const int32_t* prev, int64_t n, uint8_t* legal,

@@ -56,6 +56,8 @@ struct GameDefaults {
     static constexpr bool PAYOFF_DRAWS = false;
     static constexpr int SPARSE_K = 0;     // > 0: obs rows are one-hot with SPARSE_K known positions (observe_pos)
     static constexpr int MAX_POLICY = 0;   // > 0: the largest CS_POLICY_* id of the game's rule_action
+    // cs_policy_actions' random pick for a game without rule policies (MAX_POLICY 0 otherwise has no policy kernels)
+    static constexpr bool RANDOM_ACTIONS = false;
     static constexpr int DQ = 0;           // > 0: deals drawn ahead into a queue of this depth (cs_dq.h)
     // obs rows stored by their own lane, 16 B at a time, instead of through the wave's LDS span image: for games whose
     // occupancy is bound by LDS and whose rows are 16-B multiples (UNO: the 60 KB image per block was one block per CU)

@@ -129,6 +129,8 @@ hipError_t launch_copy_state(const Buffers& b, int64_t env, int32_t sw, int32_t 
 hipError_t launch_rng_copy(const Buffers& b, int64_t env, int32_t mtw, int32_t column, uint32_t clear_mask,
                            uint32_t* buf, int32_t load, hipStream_t s);   // cs_traj.hip
 hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, hipStream_t s);   // cs_kernels.hip
+hipError_t launch_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n,
+                                   uint8_t* win, hipStream_t s);   // cs_kernels.hip
 
 namespace ddz {   // cs_doudizhu.hip
 hipError_t launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,

@@ -11,6 +11,7 @@
 #include "cs_doudizhu.h"
 #include "cs_nolimit.h"
 #include "cs_uno.h"
+#include "cs_mahjong.h"
 
 namespace cs {
 
@@ -65,6 +66,7 @@ const GameOps* find_game(int32_t game, const cs_config* cfg)
         return p == 2 ? ops_of<Nolimit>() : nullptr;
     }
     case CS_GAME_UNO: return (np == 0 || np == Uno::P) ? ops_of<Uno>() : nullptr;   // (cs_create names the refusal)
+    case CS_GAME_MAHJONG: return (np == 0 || np == Mahjong::P) ? ops_of<Mahjong>() : nullptr;   // (as UNO)
     case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
     default: return nullptr;
     }
@@ -85,6 +87,28 @@ __global__ __launch_bounds__(BLOCK) void k_debug_rank7(const int8_t* __restrict_
 hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, hipStream_t s)
 {
     hipLaunchKernelGGL(k_debug_rank7, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cards, n, values);
+    return hipGetLastError();
+}
+
+// Test hook (cs_debug_mahjong_hu): the win judge of the Mahjong kernels (cs_mahjong_hu.h judge_hu) on arbitrary ordered
+// hands, one thread per hand
+__global__ __launch_bounds__(BLOCK) void k_debug_mahjong_hu(const uint8_t* __restrict__ hands,
+                                                            const uint8_t* __restrict__ len,
+                                                            const uint8_t* __restrict__ piles, int64_t n, uint8_t* win)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t h[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < mj::HAND_MAX; k++) h[k >> 2] |= (uint32_t)hands[i * mj::HAND_MAX + k] << (8 * (k & 3));
+    win[i] = (uint8_t)mj::judge_hu(h, (int)len[i], (int)piles[i]);
+}
+
+hipError_t launch_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n,
+                                   uint8_t* win, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_debug_mahjong_hu, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, hands, len,
+                       piles, n, win);
     return hipGetLastError();
 }
 

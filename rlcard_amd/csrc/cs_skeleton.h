@@ -585,8 +585,12 @@ __global__ __launch_bounds__(BLOCK) void k_policy_actions(const uint32_t* st, in
         } else {
             const uint64_t lg = g.legal();
             const uint32_t pr = philox_u32(seed, env_base + (uint64_t)env, t);
-            if (policy == CS_POLICY_RANDOM) a = pick_legal64(lg, pr);
-            else a = g.rule_action((uint32_t)policy, g.current(), lg, pr);
+            if constexpr (G::MAX_POLICY > 0) {
+                if (policy == CS_POLICY_RANDOM) a = pick_legal64(lg, pr);
+                else a = g.rule_action((uint32_t)policy, g.current(), lg, pr);
+            } else {
+                a = pick_legal64(lg, pr);   // (no rule policy: the ABI refuses any id but CS_POLICY_RANDOM)
+            }
         }
     }
     actions[env] = a;
@@ -687,6 +691,8 @@ static const GameOps* ops_of()
             o.rollout_policy = rollout_policy_g<G>;
             o.policy_actions = policy_actions_g<G>;
             o.max_policy = G::MAX_POLICY;
+        } else if constexpr (G::RANDOM_ACTIONS) {
+            o.policy_actions = policy_actions_g<G>;   // CS_POLICY_RANDOM only (max_policy stays 0)
         }
         return o;
     }();

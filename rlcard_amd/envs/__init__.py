@@ -1,5 +1,5 @@
 """The env registry: rlcard's plugin API (rlcard/envs/registration.py:8-89, envs/__init__.py) -- register(env_id,
-'module:Class') and make(env_id, config) -- over the engine's six games. Same ids, same config defaults and the same
+'module:Class') and make(env_id, config) -- over the engine's seven games. Same ids, same config defaults and the same
 ValueError messages for an unknown or a duplicate id."""
 import importlib
 
@@ -34,3 +34,4 @@ register('limit-holdem', 'rlcard_amd.envs.limitholdem:LimitholdemEnv')
 register('doudizhu', 'rlcard_amd.envs.doudizhu:DoudizhuEnv')
 register('no-limit-holdem', 'rlcard_amd.envs.nolimitholdem:NolimitholdemEnv')
 register('uno', 'rlcard_amd.envs.uno:UnoEnv')
+register('mahjong', 'rlcard_amd.envs.mahjong:MahjongEnv')

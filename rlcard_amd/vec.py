@@ -58,6 +58,8 @@ class VecEnv(_abi.Handle):
         np_ = int(config.get('game_num_players', 0))
         if env_id == 'uno' and np_ not in (0, 2):   # the engine answers CS_E_UNSUPPORTED (include/cardsim.h)
             raise ValueError('uno: game_num_players must be 2, got %d' % np_)
+        if env_id == 'mahjong' and np_ not in (0, 4):
+            raise ValueError('mahjong: game_num_players must be 4, got %d' % np_)
         nd = int(config.get('game_num_decks', -1))
         chips = int(config.get('chips_for_each', 0))
         self.rng_mode = config.get('rng_mode', 'mt19937')   # 'philox': fast, not the reference's deals
