@@ -29,9 +29,9 @@ enum {
 };
 
 /* game ids; names as registered by rlcard/envs/__init__.py:6-54 (CS_GAME_UNO: 'uno', two players; CS_GAME_MAHJONG:
- * 'mahjong', four players) */
+ * 'mahjong', four players; CS_GAME_GIN_RUMMY: 'gin-rummy', two players, the reference's default Settings) */
 enum { CS_GAME_BLACKJACK = 0, CS_GAME_LEDUC = 1, CS_GAME_LIMIT = 2, CS_GAME_DOUDIZHU = 3, CS_GAME_NOLIMIT = 4,
-       CS_GAME_UNO = 5, CS_GAME_MAHJONG = 6 };
+       CS_GAME_UNO = 5, CS_GAME_MAHJONG = 6, CS_GAME_GIN_RUMMY = 7 };
 
 typedef struct cs_handle cs_handle;
 
@@ -39,7 +39,7 @@ typedef struct cs_handle cs_handle;
 typedef struct {
     int32_t num_players; /* blackjack 'game_num_players' (default 1); leduc/limit/no-limit 2; doudizhu 3 (0 = default);
                             uno 2 only: any other count is CS_E_UNSUPPORTED (the reference's payoffs[1 - winner]);
-                            mahjong 4 only: any other count is CS_E_UNSUPPORTED */
+                            mahjong 4 only: any other count is CS_E_UNSUPPORTED; gin-rummy 2 only, likewise */
     int32_t num_decks;   /* blackjack 'game_num_decks' (default 1, 0 = infinite); ignored elsewhere (-1 = default) */
     int32_t chips_for_each; /* no-limit 'chips_for_each' (nolimitholdem/game.py:45-56): stack, 1..255 (0 = 100) */
     int32_t dealer_plus1;   /* no-limit 'dealer_id' + 1: 0 = None (drawn by the first game, then kept), 1..N fixed */
@@ -56,9 +56,15 @@ enum { CS_RNG_MT19937 = 0, CS_RNG_PHILOX = 1 };
 typedef struct {
     int32_t obs_dim;      /* bytes per obs row: leduc 36, limit 72, no-limit 54, blackjack 2, doudizhu 901 (landlord 790),
                              uno 240 ([4][4][15] row-major, every row holds exactly 61 ones), mahjong 816 ([6][34][4]
-                             row-major: hand, table, the four players' piles; a tile's row is 1 in columns < its count) */
+                             row-major: hand, table, the four players' piles; a tile's row is 1 in columns < its count),
+                             gin-rummy 260 ([5][52] row-major, always the CURRENT player's: hand, top discard, the other
+                             discards, the opponent's known cards, stock + the opponent's cards not known; all zero once
+                             the game is over) */
     int32_t num_actions;  /* leduc/limit 4, no-limit 5, blackjack 2, doudizhu 27472, uno 61 (8 legal bytes),
-                             mahjong 38 (5 legal bytes: tiles 0..33, pong 34, chow 35, gong 36, stand 37) */
+                             mahjong 38 (5 legal bytes: tiles 0..33, pong 34, chow 35, gong 36, stand 37),
+                             gin-rummy 110 (14 legal bytes, bits 110 and 111 always 0: score north 0, score south 1,
+                             draw 2, pick up 3, dead hand 4, gin 5, discard card c 6 + c, knock card c 58 + c, card id =
+                             rank + 13 * suit with ranks A 2 .. K and suits S H D C) */
     int32_t num_players;
     int32_t legal_bytes;  /* ceil(num_actions / 8): legal-action bitmask bytes per row */
     int32_t action_bytes; /* dtype width of rollout action rows: 1 (uint8) or 2 (int16, doudizhu) */
@@ -156,7 +162,9 @@ int cs_reset(cs_handle* h, const cs_step_out* out, void* stream);
  * np.random), and a deal or draw that finds fewer cards than it needs even after replace_deck takes the cards that are
  * there (the reference raises IndexError); Mahjong: an illegal id plays the lowest legal id (the reference raises),
  * a game already won on the deal is done = 1 at the reset row with zero rewards, and a finished game's legal mask may
- * be zero. Envs whose game was already over
+ * be zero; Gin Rummy: an illegal id plays the lowest legal id (the reference raises or corrupts its lists), the game
+ * ends (done = 1, payoffs) at the step that plays `score south`, and its state has no undo (the reference's step_back
+ * raises NotImplementedError). Envs whose game was already over
  * start a new game instead (lazy auto-reset: action ignored, done = 0, reward = 0), so an RL loop never calls
  * reset() per env. */
 int cs_step(cs_handle* h, const int32_t* actions, const cs_step_out* out, void* stream);
@@ -184,10 +192,13 @@ int cs_rollout(cs_handle* h, int32_t T, uint64_t policy_seed, uint64_t t0, uint6
  *                      without the *-wild ids (kept if nothing else is legal) -- the reference draws that pick from the
  *                      global np.random, the engine from the step's policy word with CS_POLICY_RANDOM's formula, so a
  *                      rule seat's games are a function of policy_seed
+ *                      Gin Rummy: gin-rummy-novice-rule (rlcard/models/gin_rummy_rule_models.py): gin if legal; else a
+ *                      uniform pick among the knock ids; else among the discards after which the other 10 cards have
+ *                      the least best deadwood; else among the legal ids -- every pick from the step's policy word
  *   CS_POLICY_RULE_V2  Leduc only: leduc-holdem-rule-v2 (raise on a rank match with the public card, else fold)
  * A hold'em rule that aims at an illegal action plays call for raise, fold for check and raise for call, as the reference
- * does. Rule policies exist for default 2-player Leduc, heads-up Limit hold'em and UNO; with any other game or player
- * count a rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit and on UNO, and every rule id on
+ * does. Rule policies exist for default 2-player Leduc, heads-up Limit hold'em, UNO and Gin Rummy; with any other game or
+ * player count a rule id returns CS_E_UNSUPPORTED (so does CS_POLICY_RULE_V2 on Limit, UNO and Gin Rummy, and every rule id on
  * Mahjong, for which the reference has no rule model; cs_policy_actions(CS_POLICY_RANDOM) works there). */
 enum { CS_POLICY_RANDOM = 0, CS_POLICY_RULE_V1 = 1, CS_POLICY_RULE_V2 = 2 };
 
@@ -414,7 +425,7 @@ int cs_nfsp_actions(cs_handle* h, const cs_qnet* qnet, const cs_qnet* pnet, cons
 
 /* Reservoir buffer of a handle's envs on the device (nfsp_agent.py ReservoirBuffer of (info_state, action_probs)).
  * Only best-response steps are stored and their action_probs are one-hot, so a slot holds state u8 [obs_dim] and the
- * action id. Games with more than 64 actions (DouDizhu) are CS_E_UNSUPPORTED. */
+ * action id. Games with more than 64 actions (DouDizhu, Gin Rummy) are CS_E_UNSUPPORTED. */
 typedef struct cs_reservoir cs_reservoir;
 int  cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reservoir** out);
 void cs_reservoir_destroy(cs_reservoir* r);
@@ -497,6 +508,15 @@ int cs_debug_holdem_rank7(const int8_t* cards, int64_t n, uint32_t* values, void
  * (0 / 1). All DEVICE memory; stateless (no handle). */
 int cs_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n, uint8_t* win,
                         void* stream);
+
+/* Gin Rummy meld-judge test hook: the judge of the Gin Rummy kernels (rlcard_amd/csrc/cs_gin_melds.h; the reference's
+ * utils/melding.py, judge._get_going_out_cards, round.gin) on `n` ordered hands: hands u8 [n][11] (card id = rank +
+ * 13 * suit, in hand order), len u8 [n] (cards used of each row, <= 11) -> deadwood i32 [n] (the best deadwood count of
+ * the row's cards), and for rows of 11 cards knock u64 [n] and gin u64 [n] (the knock and gin sets as card masks) and
+ * gin_card i32 [n] (gin_cards[0], -1 with an empty gin set); rows of another length get 0, 0, -1. All DEVICE memory;
+ * stateless (no handle). */
+int cs_debug_gin_melds(const uint8_t* hands, const uint8_t* len, int64_t n, int32_t* deadwood, uint64_t* knock,
+                       uint64_t* gin, int32_t* gin_card, void* stream);
 
 /* DouDizhu legal-set test hook: the legal-action bitmask the step / rollout kernels build, for `n` (hand, previous
  * play) cases: counts u8 [n][15] (cards per rank 3 .. A, 2, black joker, red joker), prev i32 [n] (the largest play

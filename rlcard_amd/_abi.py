@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get('CARDSIM_LIB', 'libcardsim.so'))  
 # the games with a restatement under oracle/ (bench.py's games; tests/test_abi.py records cs_game_info for exactly these)
 GAME_IDS = {'blackjack': 0, 'leduc-holdem': 1, 'limit-holdem': 2, 'doudizhu': 3, 'no-limit-holdem': 4}
 # games pinned by the reference's recorded streams alone
-RECORDED_GAME_IDS = {'uno': 5, 'mahjong': 6}
+RECORDED_GAME_IDS = {'uno': 5, 'mahjong': 6, 'gin-rummy': 7}
 
 
 def game_id(env_id):
@@ -131,6 +131,7 @@ def _prototypes():
         'cs_get_rng_ctl': (rc, [vp, i64, vp]),
         'cs_debug_holdem_rank7': (rc, [vp, i64, vp, vp]),
         'cs_debug_mahjong_hu': (rc, [vp, vp, vp, i64, vp, vp]),
+        'cs_debug_gin_melds': (rc, [vp, vp, i64, vp, vp, vp, vp, vp]),
         'cs_debug_ddz_legal': (rc, [vp, vp, vp, i64, vp, vp]),
         'cs_debug_set_serial_refill': (rc, [vp, i32]),
         'cs_debug_set_kernel_flags': (rc, [vp, i32]),

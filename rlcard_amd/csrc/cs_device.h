@@ -60,7 +60,8 @@ struct GameDefaults {
     static constexpr bool RANDOM_ACTIONS = false;
     static constexpr int DQ = 0;           // > 0: deals drawn ahead into a queue of this depth (cs_dq.h)
     // obs rows stored by their own lane, 16 B at a time, instead of through the wave's LDS span image: for games whose
-    // occupancy is bound by LDS and whose rows are 16-B multiples (UNO: the 60 KB image per block was one block per CU)
+    // occupancy is bound by LDS and whose rows are dword multiples (UNO: the 60 KB image per block was one block per CU;
+    // a row that is no 16-B multiple, Gin Rummy's 260 B, finds its own 16-B boundary)
     static constexpr bool OBS_DIRECT = false;
 };
 
@@ -289,6 +290,29 @@ __device__ __forceinline__ int pick_legal64(uint64_t legal, uint32_t r)
     int k = (int)__umulhi(r, (uint32_t)count);
     while (k--) legal &= legal - 1;
     return __builtin_ctzll(legal);
+}
+// A legal mask of 65..128 actions (Gin Rummy's 110 ids): id i is bit i % 64 of lo (i < 64) or hi. Games of at most 64
+// actions keep a plain uint64_t (cs_skeleton.h legal_t).
+struct Legal128 {
+    uint64_t lo, hi;
+};
+__device__ __forceinline__ bool legal_empty(const Legal128& m) { return (m.lo | m.hi) == 0ull; }
+__device__ __forceinline__ bool legal_has(const Legal128& m, int a) { return ((a < 64 ? m.lo : m.hi) >> (a & 63)) & 1ull; }
+__device__ __forceinline__ int legal_lowest(const Legal128& m)
+{
+    return m.lo ? __builtin_ctzll(m.lo) : 64 + __builtin_ctzll(m.hi);
+}
+// pick_legal64's formula over both words: the k-th set bit in id order, k = floor(r * count / 2^32)
+__device__ __forceinline__ int pick_legal128(const Legal128& legal, uint32_t r)
+{
+    const int clo = __popcll(legal.lo), count = clo + __popcll(legal.hi);
+    if (count == 0) return -1;
+    int k = (int)__umulhi(r, (uint32_t)count);
+    const bool high = k >= clo;
+    uint64_t w = high ? legal.hi : legal.lo;
+    k -= high ? clo : 0;
+    while (k--) w &= w - 1;
+    return (high ? 64 : 0) + __builtin_ctzll(w);
 }
 // the same pick for masks of at most A bits (A <= 8), branch-free: the k-th set bit after k clears of the lowest
 // (k < A), so a wave's lanes never loop to the largest k among them

@@ -132,6 +132,9 @@ hipError_t launch_debug_rank7(const int8_t* cards, int64_t n, uint32_t* values, 
 hipError_t launch_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, const uint8_t* piles, int64_t n,
                                    uint8_t* win, hipStream_t s);   // cs_kernels.hip
 
+hipError_t launch_debug_gin_melds(const uint8_t* hands, const uint8_t* len, int64_t n, int32_t* deadwood,
+                                  uint64_t* knock, uint64_t* gin, int32_t* gin_card, hipStream_t s);   // cs_kernels.hip
+
 namespace ddz {   // cs_doudizhu.hip
 hipError_t launch_seed(const Buffers& b, const uint32_t* keys_dev, const int32_t* klen_dev, int64_t first,
                        int64_t count, hipStream_t s);

@@ -12,6 +12,7 @@
 #include "cs_nolimit.h"
 #include "cs_uno.h"
 #include "cs_mahjong.h"
+#include "cs_gin_rummy.h"
 
 namespace cs {
 
@@ -67,6 +68,7 @@ const GameOps* find_game(int32_t game, const cs_config* cfg)
     }
     case CS_GAME_UNO: return (np == 0 || np == Uno::P) ? ops_of<Uno>() : nullptr;   // (cs_create names the refusal)
     case CS_GAME_MAHJONG: return (np == 0 || np == Mahjong::P) ? ops_of<Mahjong>() : nullptr;   // (as UNO)
+    case CS_GAME_GIN_RUMMY: return (np == 0 || np == GinRummy::P) ? ops_of<GinRummy>() : nullptr;   // (as UNO)
     case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
     default: return nullptr;
     }
@@ -109,6 +111,39 @@ hipError_t launch_debug_mahjong_hu(const uint8_t* hands, const uint8_t* len, con
 {
     hipLaunchKernelGGL(k_debug_mahjong_hu, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, hands, len,
                        piles, n, win);
+    return hipGetLastError();
+}
+
+// Test hook (cs_debug_gin_melds): the meld judge of the Gin Rummy kernels (cs_gin_melds.h) on arbitrary ordered hands,
+// one thread per hand
+__global__ __launch_bounds__(BLOCK) void k_debug_gin_melds(const uint8_t* __restrict__ hands,
+                                                           const uint8_t* __restrict__ len, int64_t n,
+                                                           int32_t* deadwood, uint64_t* knock, uint64_t* gin_o,
+                                                           int32_t* gin_card)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t h[gin::HAND_WORDS] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < gin::HAND_MAX; k++) h[k >> 2] |= (uint32_t)hands[i * gin::HAND_MAX + k] << (8 * (k & 3));
+    const int ln = len[i] <= gin::HAND_MAX ? (int)len[i] : gin::HAND_MAX;
+    deadwood[i] = gin::best_deadwood(h, ln);
+    uint64_t kn = 0, g = 0;
+    int card = -1;
+    if (ln == gin::HAND_MAX) {
+        gin::going_out<true>(h, ln, &kn, &g);
+        card = gin::gin_card(h, ln);
+    }
+    knock[i] = kn;
+    gin_o[i] = g;
+    gin_card[i] = card;
+}
+
+hipError_t launch_debug_gin_melds(const uint8_t* hands, const uint8_t* len, int64_t n, int32_t* deadwood,
+                                  uint64_t* knock, uint64_t* gin_o, int32_t* gin_card, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_debug_gin_melds, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, hands, len, n,
+                       deadwood, knock, gin_o, gin_card);
     return hipGetLastError();
 }
 

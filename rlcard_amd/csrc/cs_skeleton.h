@@ -18,6 +18,10 @@ namespace cs {
 constexpr int BLOCK = 256;
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;
 
+// a game's legal mask: one 64-bit word up to 64 actions, two above (cs_device.h Legal128)
+template <class G>
+using legal_t = std::conditional_t<(G::A > 64), Legal128, uint64_t>;
+
 struct LaneCtx {
     int lane, wid;
     int64_t env, wave_first;
@@ -79,12 +83,51 @@ __device__ __forceinline__ void write_obs_rows16(uint8_t* o, const uint32_t (&bi
 template <class G>
 __device__ __forceinline__ void write_obs_direct(uint8_t* o, const uint32_t (&bits)[G::NB]);   // (below)
 
+// The same for rows that are a dword multiple but no 16-B multiple (Gin Rummy's 260 B): row r starts at r * OBS, so the
+// rows' 16-B phases differ and each lane decides for its own. H dwords (0..3) bring the address to a 16-B boundary,
+// then nontemporal 16-B stores, then the dwords left over; a tensor that is not dword aligned takes byte stores.
+template <class G, int H>
+__device__ __forceinline__ void write_obs_row16_head(uint8_t* o, const uint32_t (&bits)[G::NB])
+{
+    constexpr int D = G::OBS / 4, Q = (D - H) / 4;
+    auto dword = [&](int j) { return RowWriter<G::OBS>::expand4(bits[j / 8] >> (4 * (j % 8))); };
+#pragma unroll
+    for (int j = 0; j < H; j++) out_store((uint32_t*)o + j, dword(j));
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        uint4 v;
+        v.x = dword(H + 4 * q);
+        v.y = dword(H + 4 * q + 1);
+        v.z = dword(H + 4 * q + 2);
+        v.w = dword(H + 4 * q + 3);
+        out_store16((uint4*)((uint32_t*)o + H) + q, v);
+    }
+#pragma unroll
+    for (int j = H + 4 * Q; j < D; j++) out_store((uint32_t*)o + j, dword(j));
+}
+template <class G>
+__device__ __forceinline__ void write_obs_rows16_any(uint8_t* o, const uint32_t (&bits)[G::NB])
+{
+    static_assert(!G::RAW_OBS && G::OBS % 4 == 0 && G::OBS >= 32, "direct rows: 0/1 bytes, a dword multiple per row");
+    const uint32_t a = (uint32_t)(uintptr_t)o & 15u;
+    if (a == 0u) write_obs_row16_head<G, 0>(o, bits);
+    else if (a == 12u) write_obs_row16_head<G, 1>(o, bits);
+    else if (a == 8u) write_obs_row16_head<G, 2>(o, bits);
+    else if (a == 4u) write_obs_row16_head<G, 3>(o, bits);
+    else {
+#pragma unroll 4
+        for (int k = 0; k < G::OBS; k++) o[k] = (uint8_t)((bits[k >> 5] >> (k & 31)) & 1u);
+    }
+}
+
 // obs rows: staged + coalesced when the row is a dword multiple, per-lane bytes otherwise
 template <class G, int ROWS = WAVE>
 __device__ __forceinline__ void emit_obs(uint32_t* lds, const uint32_t (&bits)[G::NB], uint8_t* obs, int64_t row0, int flags,
                                          const LaneCtx& c)
 {
-    if constexpr (G::OBS_DIRECT) {
+    if constexpr (G::OBS_DIRECT && G::OBS % 16 != 0) {
+        if (c.valid) write_obs_rows16_any<G>(obs + (row0 + c.lane) * G::OBS, bits);   // (decided per row)
+    } else if constexpr (G::OBS_DIRECT) {
         if (c.valid) {   // (the row stride is a 16-B multiple: the tensor's alignment is every row's)
             uint8_t* o = obs + (row0 + c.lane) * G::OBS;
             if ((((uintptr_t)o) & 15u) == 0) write_obs_rows16<G>(o, bits);
@@ -131,6 +174,16 @@ __device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, uint64_t
 {
 #pragma unroll
     for (int k = 0; k < G::LB; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg >> (8 * k)));
+}
+
+template <class G>
+__device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, const Legal128& lg)
+{
+    static_assert(G::LB > 8 && G::LB <= 16, "two-word legal rows");
+#pragma unroll
+    for (int k = 0; k < 8; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg.lo >> (8 * k)));
+#pragma unroll
+    for (int k = 8; k < G::LB; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg.hi >> (8 * (k - 8))));
 }
 
 template <class G>
@@ -462,15 +515,16 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
 
         const int64_t rowbase = (int64_t)t * n;
         const int p = g.current();
-        const uint64_t lg = g.legal();
+        const legal_t<G> lg = g.legal();
         uint32_t bits[G::NB];
         g.observe(p, bits);
         // each row stored where it is produced (round 5: the rows after the step's refill / restage loads ran 6-7 %
         // slower on every torch allocation, profiles/EXPERIMENTS.md)
         const uint32_t pr = pol.at(seed, genv0, t0 + (uint64_t)t, t == 0);
         int a;
-        static_assert(G::A <= 64, "the policy pick takes a 64-bit legal mask");
-        if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
+        static_assert(G::A <= 128, "the policy pick takes a legal mask of one or two 64-bit words");
+        if constexpr (G::A > 64) a = pick_legal128(lg, pr);
+        else if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
         else if constexpr (G::A <= 32) a = pick_legal32((uint32_t)lg, pr);
         else a = pick_legal64(lg, pr);
         if constexpr (POL) {
@@ -578,7 +632,16 @@ __global__ __launch_bounds__(BLOCK) void k_policy_actions(const uint32_t* st, in
     g.load(st, n, env);
     int a = -1;
     if (!g.is_over()) {
-        if constexpr (G::A <= 32) {
+        if constexpr (G::A > 64) {
+            const Legal128 lg = g.legal();
+            const uint32_t pr = philox_u32(seed, env_base + (uint64_t)env, t);
+            if constexpr (G::MAX_POLICY > 0) {
+                if (policy == CS_POLICY_RANDOM) a = pick_legal128(lg, pr);
+                else a = g.rule_action((uint32_t)policy, g.current(), lg, pr);
+            } else {
+                a = pick_legal128(lg, pr);   // (no rule policy: the ABI refuses any id but CS_POLICY_RANDOM)
+            }
+        } else if constexpr (G::A <= 32) {
             const uint32_t lg = (uint32_t)g.legal();
             if (policy == CS_POLICY_RANDOM) a = pick_legal_small<G::A>(lg, philox_u32(seed, env_base + (uint64_t)env, t));
             else a = g.rule_action((uint32_t)policy, g.current(), lg);

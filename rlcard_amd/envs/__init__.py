@@ -1,5 +1,5 @@
 """The env registry: rlcard's plugin API (rlcard/envs/registration.py:8-89, envs/__init__.py) -- register(env_id,
-'module:Class') and make(env_id, config) -- over the engine's seven games. Same ids, same config defaults and the same
+'module:Class') and make(env_id, config) -- over the engine's eight games. Same ids, same config defaults and the same
 ValueError messages for an unknown or a duplicate id."""
 import importlib
 
@@ -35,3 +35,4 @@ register('doudizhu', 'rlcard_amd.envs.doudizhu:DoudizhuEnv')
 register('no-limit-holdem', 'rlcard_amd.envs.nolimitholdem:NolimitholdemEnv')
 register('uno', 'rlcard_amd.envs.uno:UnoEnv')
 register('mahjong', 'rlcard_amd.envs.mahjong:MahjongEnv')
+register('gin-rummy', 'rlcard_amd.envs.gin_rummy:GinRummyEnv')

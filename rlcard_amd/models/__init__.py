@@ -8,3 +8,5 @@ register(model_id='leduc-holdem-rule-v1', entry_point='rlcard_amd.models.leducho
 register(model_id='leduc-holdem-rule-v2', entry_point='rlcard_amd.models.leducholdem_rule_models:LeducHoldemRuleModelV2')
 register(model_id='limit-holdem-rule-v1', entry_point='rlcard_amd.models.limitholdem_rule_models:LimitholdemRuleModelV1')
 register(model_id='uno-rule-v1', entry_point='rlcard_amd.models.uno_rule_models:UNORuleModelV1')
+register(model_id='gin-rummy-novice-rule',
+         entry_point='rlcard_amd.models.gin_rummy_rule_models:GinRummyNoviceRuleModel')

@@ -4,7 +4,7 @@ import importlib
 
 # names VecEnv.rollout(policies=...) accepts -> the engine's policy id (include/cardsim.h CS_POLICY_*)
 POLICY_IDS = {'random': 0, 'leduc-holdem-rule-v1': 1, 'leduc-holdem-rule-v2': 2, 'limit-holdem-rule-v1': 1,
-              'uno-rule-v1': 1}
+              'uno-rule-v1': 1, 'gin-rummy-novice-rule': 1}
 
 
 def policy_id_of(policy):

@@ -156,7 +156,8 @@ static void abi_host()
     memset(&cfg, 0, sizeof(cfg));
     cfg.num_decks = -1;
     for (int g = 0; g < 5; g++) EXPECT(cs_game_info_get(g, &cfg, &info) == CS_OK && info.obs_dim > 0);
-    EXPECT(cs_game_info_get(7, &cfg, &info) != CS_OK);
+    EXPECT(cs_game_info_get(CS_GAME_GIN_RUMMY, &cfg, &info) == CS_OK && info.legal_bytes == 14);
+    EXPECT(cs_game_info_get(8, &cfg, &info) != CS_OK);
     EXPECT(cs_game_info_get(CS_GAME_LEDUC, &cfg, nullptr) == CS_E_INVALID);
     // Blackjack shoes / big tables (cs_blackjack_shoe.hip): 8 decks x 7 players; 9 decks, 8 players and the
     // Philox byte stream are refused
@@ -198,6 +199,7 @@ static void abi_host()
     EXPECT(cs_copy_env_state(nullptr, 0, nullptr, nullptr) == CS_E_INVALID);
     EXPECT(cs_debug_holdem_rank7(nullptr, 1, nullptr, nullptr) == CS_E_INVALID);
     EXPECT(cs_debug_mahjong_hu(nullptr, nullptr, nullptr, 1, nullptr, nullptr) == CS_E_INVALID);
+    EXPECT(cs_debug_gin_melds(nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr) == CS_E_INVALID);
     EXPECT(cs_debug_ddz_legal(nullptr, nullptr, nullptr, 1, nullptr, nullptr) == CS_E_INVALID);
     EXPECT(cs_debug_set_kernel_flags(nullptr, 0) == CS_E_INVALID);
     EXPECT(strlen(cs_version()) > 0);
