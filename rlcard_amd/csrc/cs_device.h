@@ -63,6 +63,10 @@ struct GameDefaults {
     // occupancy is bound by LDS and whose rows are dword multiples (UNO: the 60 KB image per block was one block per CU;
     // a row that is no 16-B multiple, Gin Rummy's 260 B, finds its own 16-B boundary)
     static constexpr bool OBS_DIRECT = false;
+    // > 0: a direct 0/1 row that holds RAW_SPAN_LEN raw bytes from byte RAW_SPAN_AT on (Bridge's bidding_rep of action
+    // ids): observe() gives the bitmap in G::NBITS words, zero over the span, then the span's bytes four per word, and
+    // the row may have any length (cs_skeleton.h write_obs_mixed)
+    static constexpr int RAW_SPAN_LEN = 0, RAW_SPAN_AT = 0;
 };
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y)

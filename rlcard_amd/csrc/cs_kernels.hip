@@ -13,6 +13,7 @@
 #include "cs_uno.h"
 #include "cs_mahjong.h"
 #include "cs_gin_rummy.h"
+#include "cs_bridge.h"
 
 namespace cs {
 
@@ -69,6 +70,7 @@ const GameOps* find_game(int32_t game, const cs_config* cfg)
     case CS_GAME_UNO: return (np == 0 || np == Uno::P) ? ops_of<Uno>() : nullptr;   // (cs_create names the refusal)
     case CS_GAME_MAHJONG: return (np == 0 || np == Mahjong::P) ? ops_of<Mahjong>() : nullptr;   // (as UNO)
     case CS_GAME_GIN_RUMMY: return (np == 0 || np == GinRummy::P) ? ops_of<GinRummy>() : nullptr;   // (as UNO)
+    case CS_GAME_BRIDGE: return (np == 0 || np == Bridge::P) ? ops_of<Bridge>() : nullptr;   // (as UNO)
     case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
     default: return nullptr;
     }

@@ -26,6 +26,17 @@
 #ifndef CS_PROF_NO_SKIP
 #define CS_PROF_NO_SKIP 0      // Limit / No-limit: no skip scan of the 42 undealt draws
 #endif
+#ifndef CS_PROF_MIXED_WRITER
+// Bridge's obs rows (cs_skeleton.h write_obs_mixed; right outputs): 0 the product's aligned pieces, 1 a byte loop the
+// compiler merges into unaligned wide stores (profiles/EXPERIMENTS.md B-1 has the other two writers measured)
+#define CS_PROF_MIXED_WRITER 0
+#endif
+#ifndef CS_PROF_MIXED_NT
+#define CS_PROF_MIXED_NT 0     // Bridge's obs rows with nontemporal stores (write_obs_mixed_head; right outputs)
+#endif
+#ifndef CS_PROF_BRIDGE_WAVES
+#define CS_PROF_BRIDGE_WAVES 0 // > 0: Bridge k_rollout's waves per SIMD instead of Bridge::MIN_WAVES (right outputs)
+#endif
 #ifndef CS_PROF_DDZ
 #define CS_PROF_DDZ 0          // DouDizhu k_rollout2: bit 0 no legal rows, bit 1 no obs rows
 #endif

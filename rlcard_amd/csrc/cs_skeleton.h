@@ -120,12 +120,113 @@ __device__ __forceinline__ void write_obs_rows16_any(uint8_t* o, const uint32_t 
     }
 }
 
+// Rows of any length that hold a raw-byte field among their 0/1 bytes (G::RAW_SPAN_LEN > 0, Bridge's 573 B): row r
+// starts at r * OBS, so a wave's lanes see every byte phase and every 16-B phase, and a row shares a 16-B piece with its
+// neighbour at both ends: a lane stores its own bytes only. mixed_dword is dword j of the row's value stream (bytes 4 j
+// .. 4 j + 3; zero past the row), j a constant after unrolling, so no bitmap word is indexed dynamically.
+template <class G>
+__device__ __forceinline__ uint32_t mixed_dword(const uint32_t (&bits)[G::NB], int j)
+{
+    constexpr int ND = (G::OBS + 3) / 4;
+    static_assert(ND <= 8 * G::NBITS && G::NB == G::NBITS + G::RAW_SPAN_LEN / 4 && G::RAW_SPAN_LEN % 4 == 0 &&
+                      G::RAW_SPAN_AT + G::RAW_SPAN_LEN <= G::OBS,
+                  "mixed rows: the bitmap words, then the span's bytes");
+    if (j >= ND) return 0u;
+    uint32_t v = RowWriter<4>::expand4(bits[j / 8] >> (4 * (j % 8)));
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int sb = 4 * j + i - G::RAW_SPAN_AT;   // this byte's place in the span
+        if (sb >= 0 && sb < G::RAW_SPAN_LEN) v |= ((bits[G::NBITS + sb / 4] >> (8 * (sb % 4))) & 255u) << (8 * i);
+    }
+    return v;
+}
+// The row from its first dword-aligned byte on: hb (0..3) bytes before it were stored by the caller, so stream dword i
+// is alignbyte(dword i + 1, dword i, hb), one more VALU instruction per dword. H dwords (0..3, a template argument: the
+// indices stay constants) bring the address to a 16-B boundary, then 16-B stores, then the dwords and bytes left over:
+// (OBS - hb) / 4 whole dwords, NDMIN or one more, and at most three bytes.
+// The stores are plain, not nontemporal: neighbouring rows share cache lines at both ends and a lane's 16-B pieces are
+// 573 B apart from the next lane's, so the lines fill up in L2 over many instructions; streamed past the caches the same
+// stores measured about six times slower (profiles/EXPERIMENTS.md B-1; cs_prof.h CS_PROF_MIXED_NT).
+template <class T>
+__device__ __forceinline__ void mixed_store(T* p, T v)
+{
+#if CS_PROF_MIXED_NT
+    out_store(p, v);
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ void mixed_store16(uint4* p, const uint4& v)
+{
+#if CS_PROF_MIXED_NT
+    out_store16(p, v);
+#else
+    *p = v;
+#endif
+}
+template <class G, int H>
+__device__ __forceinline__ void write_obs_mixed_head(uint8_t* o, const uint32_t (&bits)[G::NB], uint32_t hb)
+{
+    constexpr int NDMIN = (G::OBS - 3) / 4, Q = (NDMIN - H) / 4;
+    uint32_t* od = (uint32_t*)(o + hb);
+    uint32_t lo = mixed_dword<G>(bits, 0);
+    auto next = [&](int i) {
+        const uint32_t hi = mixed_dword<G>(bits, i + 1);
+        const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, hb);
+        lo = hi;
+        return v;
+    };
+#pragma unroll
+    for (int j = 0; j < H; j++) mixed_store(od + j, next(j));
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        uint4 v;
+        v.x = next(H + 4 * q);
+        v.y = next(H + 4 * q + 1);
+        v.z = next(H + 4 * q + 2);
+        v.w = next(H + 4 * q + 3);
+        mixed_store16((uint4*)(od + H) + q, v);
+    }
+#pragma unroll
+    for (int j = H + 4 * Q; j < NDMIN; j++) mixed_store(od + j, next(j));
+    const uint32_t sa = next(NDMIN), sb = next(NDMIN + 1);
+    const uint32_t nd = ((uint32_t)G::OBS - hb) >> 2, tb = (uint32_t)G::OBS - hb - 4u * nd;
+    const bool more = nd > (uint32_t)NDMIN;
+    if (more) mixed_store(od + NDMIN, sa);
+    const uint32_t tail = more ? sb : sa;
+    uint8_t* ot = (uint8_t*)(od + nd);
+    if (tb > 0u) mixed_store(ot, (uint8_t)tail);
+    if (tb > 1u) mixed_store(ot + 1, (uint8_t)(tail >> 8));
+    if (tb > 2u) mixed_store(ot + 2, (uint8_t)(tail >> 16));
+}
+template <class G>
+__device__ __forceinline__ void write_obs_mixed(uint8_t* o, const uint32_t (&bits)[G::NB])
+{
+#if CS_PROF_MIXED_WRITER == 1   // A/B: the row as a byte loop, which the compiler merges into unaligned wide stores
+    write_obs_direct<G>(o, bits);
+#else
+    const uint32_t hb = (0u - (uint32_t)(uintptr_t)o) & 3u;   // bytes up to the first dword boundary
+    const uint32_t d0 = mixed_dword<G>(bits, 0);
+    if (hb > 0u) mixed_store(o, (uint8_t)d0);
+    if (hb > 1u) mixed_store(o + 1, (uint8_t)(d0 >> 8));
+    if (hb > 2u) mixed_store(o + 2, (uint8_t)(d0 >> 16));
+    const uint32_t a = (uint32_t)(uintptr_t)(o + hb) & 15u;
+    if (a == 0u) write_obs_mixed_head<G, 0>(o, bits, hb);
+    else if (a == 12u) write_obs_mixed_head<G, 1>(o, bits, hb);
+    else if (a == 8u) write_obs_mixed_head<G, 2>(o, bits, hb);
+    else write_obs_mixed_head<G, 3>(o, bits, hb);
+#endif
+}
+
 // obs rows: staged + coalesced when the row is a dword multiple, per-lane bytes otherwise
 template <class G, int ROWS = WAVE>
 __device__ __forceinline__ void emit_obs(uint32_t* lds, const uint32_t (&bits)[G::NB], uint8_t* obs, int64_t row0, int flags,
                                          const LaneCtx& c)
 {
-    if constexpr (G::OBS_DIRECT && G::OBS % 16 != 0) {
+    if constexpr (G::RAW_SPAN_LEN > 0) {
+        static_assert(G::OBS_DIRECT && !G::RAW_OBS && G::OBS >= 32, "mixed rows are stored by their own lane");
+        if (c.valid) write_obs_mixed<G>(obs + (row0 + c.lane) * G::OBS, bits);
+    } else if constexpr (G::OBS_DIRECT && G::OBS % 16 != 0) {
         if (c.valid) write_obs_rows16_any<G>(obs + (row0 + c.lane) * G::OBS, bits);   // (decided per row)
     } else if constexpr (G::OBS_DIRECT) {
         if (c.valid) {   // (the row stride is a 16-B multiple: the tensor's alignment is every row's)
@@ -156,7 +257,16 @@ __device__ __forceinline__ void emit_obs(uint32_t* lds, const uint32_t (&bits)[G
 template <class G>
 __device__ __forceinline__ void write_obs_direct(uint8_t* o, const uint32_t (&bits)[G::NB])
 {
-    if constexpr (G::RAW_OBS) {
+    if constexpr (G::RAW_SPAN_LEN > 0) {   // (mixed rows, any alignment: a byte loop; the compiler merges neighbours)
+#pragma unroll
+        for (int j = 0; j < (G::OBS + 3) / 4; j++) {
+            const uint32_t v = mixed_dword<G>(bits, j);
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if (4 * j + i < G::OBS) o[4 * j + i] = (uint8_t)(v >> (8 * i));
+            }
+        }
+    } else if constexpr (G::RAW_OBS) {
 #pragma unroll
         for (int k = 0; k < G::OBS; k++) o[k] = (uint8_t)(bits[k >> 2] >> (8 * (k & 3)));
     } else if constexpr (G::OBS % 4 == 0) {

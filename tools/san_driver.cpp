@@ -157,7 +157,8 @@ static void abi_host()
     cfg.num_decks = -1;
     for (int g = 0; g < 5; g++) EXPECT(cs_game_info_get(g, &cfg, &info) == CS_OK && info.obs_dim > 0);
     EXPECT(cs_game_info_get(CS_GAME_GIN_RUMMY, &cfg, &info) == CS_OK && info.legal_bytes == 14);
-    EXPECT(cs_game_info_get(8, &cfg, &info) != CS_OK);
+    EXPECT(cs_game_info_get(CS_GAME_BRIDGE, &cfg, &info) == CS_OK && info.legal_bytes == 12 && info.obs_dim == 573);
+    EXPECT(cs_game_info_get(9, &cfg, &info) != CS_OK);
     EXPECT(cs_game_info_get(CS_GAME_LEDUC, &cfg, nullptr) == CS_E_INVALID);
     // Blackjack shoes / big tables (cs_blackjack_shoe.hip): 8 decks x 7 players; 9 decks, 8 players and the
     // Philox byte stream are refused
