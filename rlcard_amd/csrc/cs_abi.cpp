@@ -129,6 +129,8 @@ int cs_game_info_get(int32_t game, const cs_config* cfg, cs_game_info* info)
         return fail(CS_E_UNSUPPORTED, "gin-rummy: game_num_players must be 2 (the reference's game is two-handed)");
     if (!ops && game == CS_GAME_BRIDGE)
         return fail(CS_E_UNSUPPORTED, "bridge: game_num_players must be 4 (the reference's game is four-handed)");
+    if (!ops && game == CS_GAME_SCOUT)
+        return fail(CS_E_UNSUPPORTED, "scout: game_num_players must be 4 (the reference's env builds a four-player game)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     *info = ops->info;
     return CS_OK;
@@ -150,6 +152,8 @@ int cs_create(cs_handle** out, int32_t game, int64_t num_envs, int32_t device, c
         return fail(CS_E_UNSUPPORTED, "gin-rummy: game_num_players must be 2 (the reference's game is two-handed)");
     if (!ops && game == CS_GAME_BRIDGE)
         return fail(CS_E_UNSUPPORTED, "bridge: game_num_players must be 4 (the reference's game is four-handed)");
+    if (!ops && game == CS_GAME_SCOUT)
+        return fail(CS_E_UNSUPPORTED, "scout: game_num_players must be 4 (the reference's env builds a four-player game)");
     if (!ops) return fail(CS_E_UNSUPPORTED, "unsupported game or game config");
     const cs_game_info& info = ops->info;
     int ndev = 0;
@@ -467,7 +471,7 @@ static int qnet_check(const cs_handle* h, const cs_qnet* net, const void* obs, i
     if (!h || !net || !obs) return fail(CS_E_INVALID, "null argument");
     const cs_game_info& info = h->ops->info;
     if (info.num_actions > 64)
-        return fail(CS_E_UNSUPPORTED, "the Q-network kernel takes games of at most 64 actions (gin-rummy has 110, bridge 91)");
+        return fail(CS_E_UNSUPPORTED, "the Q-network kernel takes games of at most 64 actions (gin-rummy has 110, bridge 91, scout 204)");
     if (net->in_dim != info.obs_dim || net->num_actions != info.num_actions)
         return fail(CS_E_INVALID, "cs_qnet: in_dim / num_actions are not the handle's game's");
     if (net->num_hidden < 1 || net->num_hidden > CS_QNET_MAX_HIDDEN)
@@ -522,7 +526,7 @@ int cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out)
     const cs_game_info& info = h->ops->info;
     if (info.legal_bytes > 16) return fail(CS_E_UNSUPPORTED, "cs_replay: legal masks of at most 16 bytes");
     if (info.num_actions > 64)   // (the replay feeds the Q-network kernel, which takes at most 64 actions)
-        return fail(CS_E_UNSUPPORTED, "cs_replay: games of at most 64 actions (gin-rummy has 110, bridge 91)");
+        return fail(CS_E_UNSUPPORTED, "cs_replay: games of at most 64 actions (gin-rummy has 110, bridge 91, scout 204)");
     int r = set_device(h);
     if (r != CS_OK) return r;
     const int64_t O = info.obs_dim, LB = info.legal_bytes, NP = h->b.n * info.num_players, cap = capacity;
@@ -664,7 +668,7 @@ int cs_reservoir_create(cs_handle* h, int64_t capacity, uint64_t seed, cs_reserv
     if (capacity <= 0) return fail(CS_E_INVALID, "capacity must be positive");
     const cs_game_info& info = h->ops->info;
     if (info.num_actions > 64)
-        return fail(CS_E_UNSUPPORTED, "cs_reservoir: games of at most 64 actions (gin-rummy has 110, bridge 91)");
+        return fail(CS_E_UNSUPPORTED, "cs_reservoir: games of at most 64 actions (gin-rummy has 110, bridge 91, scout 204)");
     int rc = set_device(h);
     if (rc != CS_OK) return rc;
     const int64_t O = info.obs_dim, cap = capacity;

@@ -318,6 +318,37 @@ __device__ __forceinline__ int pick_legal128(const Legal128& legal, uint32_t r)
     while (k--) w &= w - 1;
     return (high ? 64 : 0) + __builtin_ctzll(w);
 }
+// A legal mask of 129..256 actions (Scout's 204 ids): id i is bit i % 64 of w[i / 64]. The words are only ever indexed
+// by constants, so the mask lives in registers.
+struct Legal256 {
+    uint64_t w[4];
+};
+__device__ __forceinline__ bool legal_empty(const Legal256& m) { return (m.w[0] | m.w[1] | m.w[2] | m.w[3]) == 0ull; }
+__device__ __forceinline__ uint64_t legal_word(const Legal256& m, int k)
+{
+    return k == 0 ? m.w[0] : (k == 1 ? m.w[1] : (k == 2 ? m.w[2] : m.w[3]));
+}
+__device__ __forceinline__ bool legal_has(const Legal256& m, int a) { return (legal_word(m, a >> 6) >> (a & 63)) & 1ull; }
+__device__ __forceinline__ int legal_lowest(const Legal256& m)
+{
+    if (m.w[0]) return __builtin_ctzll(m.w[0]);
+    if (m.w[1]) return 64 + __builtin_ctzll(m.w[1]);
+    if (m.w[2]) return 128 + __builtin_ctzll(m.w[2]);
+    return 192 + __builtin_ctzll(m.w[3]);
+}
+// pick_legal64's formula over the four words: the k-th set bit in id order, k = floor(r * count / 2^32)
+__device__ __forceinline__ int pick_legal256(const Legal256& legal, uint32_t r)
+{
+    const int c0 = __popcll(legal.w[0]), c1 = c0 + __popcll(legal.w[1]), c2 = c1 + __popcll(legal.w[2]);
+    const int count = c2 + __popcll(legal.w[3]);
+    if (count == 0) return -1;
+    int k = (int)__umulhi(r, (uint32_t)count);
+    const int q = k < c0 ? 0 : (k < c1 ? 1 : (k < c2 ? 2 : 3));
+    uint64_t w = legal_word(legal, q);
+    k -= q == 0 ? 0 : (q == 1 ? c0 : (q == 2 ? c1 : c2));
+    while (k--) w &= w - 1;
+    return 64 * q + __builtin_ctzll(w);
+}
 // the same pick for masks of at most A bits (A <= 8), branch-free: the k-th set bit after k clears of the lowest
 // (k < A), so a wave's lanes never loop to the largest k among them
 template <int A>

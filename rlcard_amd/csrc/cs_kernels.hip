@@ -14,6 +14,7 @@
 #include "cs_mahjong.h"
 #include "cs_gin_rummy.h"
 #include "cs_bridge.h"
+#include "cs_scout.h"
 
 namespace cs {
 
@@ -71,6 +72,7 @@ const GameOps* find_game(int32_t game, const cs_config* cfg)
     case CS_GAME_MAHJONG: return (np == 0 || np == Mahjong::P) ? ops_of<Mahjong>() : nullptr;   // (as UNO)
     case CS_GAME_GIN_RUMMY: return (np == 0 || np == GinRummy::P) ? ops_of<GinRummy>() : nullptr;   // (as UNO)
     case CS_GAME_BRIDGE: return (np == 0 || np == Bridge::P) ? ops_of<Bridge>() : nullptr;   // (as UNO)
+    case CS_GAME_SCOUT: return (np == 0 || np == Scout::P) ? ops_of<Scout>() : nullptr;   // (as UNO)
     case CS_GAME_DOUDIZHU: return (np == 0 || np == ddz::P) ? ddz_ops() : nullptr;
     default: return nullptr;
     }

@@ -37,6 +37,17 @@
 #ifndef CS_PROF_BRIDGE_WAVES
 #define CS_PROF_BRIDGE_WAVES 0 // > 0: Bridge k_rollout's waves per SIMD instead of Bridge::MIN_WAVES (right outputs)
 #endif
+#ifndef CS_PROF_MIXED16_NT
+#define CS_PROF_MIXED16_NT 0   // Scout's obs rows (write_obs_mixed16) with nontemporal stores (right outputs)
+#endif
+#ifndef CS_PROF_SCOUT_MASK
+// Scout's legal mask (cs_scout.h; right outputs): 0 the product (built once per step from the 15 neighbour comparisons,
+// kept in the lane's LDS scratch), 1 rebuilt by every legal() call, 2 once per step but slice by slice
+#define CS_PROF_SCOUT_MASK 0
+#endif
+#ifndef CS_PROF_SCOUT_WAVES
+#define CS_PROF_SCOUT_WAVES 0  // > 0: Scout k_rollout's waves per SIMD instead of Scout::MIN_WAVES (right outputs)
+#endif
 #ifndef CS_PROF_DDZ
 #define CS_PROF_DDZ 0          // DouDizhu k_rollout2: bit 0 no legal rows, bit 1 no obs rows
 #endif

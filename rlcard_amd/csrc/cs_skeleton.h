@@ -18,9 +18,9 @@ namespace cs {
 constexpr int BLOCK = 256;
 constexpr int WAVES_PER_BLOCK = BLOCK / WAVE;
 
-// a game's legal mask: one 64-bit word up to 64 actions, two above (cs_device.h Legal128)
+// a game's legal mask: one 64-bit word up to 64 actions, two up to 128 (cs_device.h Legal128), four up to 256 (Legal256)
 template <class G>
-using legal_t = std::conditional_t<(G::A > 64), Legal128, uint64_t>;
+using legal_t = std::conditional_t<(G::A > 128), Legal256, std::conditional_t<(G::A > 64), Legal128, uint64_t>>;
 
 struct LaneCtx {
     int lane, wid;
@@ -199,6 +199,28 @@ __device__ __forceinline__ void write_obs_mixed_head(uint8_t* o, const uint32_t 
     if (tb > 1u) mixed_store(ot + 1, (uint8_t)(tail >> 8));
     if (tb > 2u) mixed_store(ot + 2, (uint8_t)(tail >> 16));
 }
+// Mixed rows that are a 16-B multiple (Scout's 688 B): the row stride keeps the tensor's alignment, so an aligned tensor
+// takes OBS / 16 whole 16-B stores per row and none of the phase work above. Plain stores, as for the rows above: a
+// lane's pieces are 688 B apart from the next lane's, and streamed past the caches they measured 5.7 times slower
+// (profiles/EXPERIMENTS.md SC-1; cs_prof.h CS_PROF_MIXED16_NT)
+template <class G>
+__device__ __forceinline__ void write_obs_mixed16(uint8_t* o, const uint32_t (&bits)[G::NB])
+{
+    static_assert(G::RAW_SPAN_LEN > 0 && G::OBS % 16 == 0, "mixed rows of whole 16-B pieces");
+#pragma unroll
+    for (int q = 0; q < G::OBS / 16; q++) {
+        uint4 v;
+        v.x = mixed_dword<G>(bits, 4 * q);
+        v.y = mixed_dword<G>(bits, 4 * q + 1);
+        v.z = mixed_dword<G>(bits, 4 * q + 2);
+        v.w = mixed_dword<G>(bits, 4 * q + 3);
+#if CS_PROF_MIXED16_NT
+        out_store16((uint4*)o + q, v);
+#else
+        *((uint4*)o + q) = v;
+#endif
+    }
+}
 template <class G>
 __device__ __forceinline__ void write_obs_mixed(uint8_t* o, const uint32_t (&bits)[G::NB])
 {
@@ -223,7 +245,10 @@ template <class G, int ROWS = WAVE>
 __device__ __forceinline__ void emit_obs(uint32_t* lds, const uint32_t (&bits)[G::NB], uint8_t* obs, int64_t row0, int flags,
                                          const LaneCtx& c)
 {
-    if constexpr (G::RAW_SPAN_LEN > 0) {
+    if constexpr (G::RAW_SPAN_LEN > 0 && G::OBS % 16 == 0) {
+        static_assert(G::OBS_DIRECT && !G::RAW_OBS, "mixed rows are stored by their own lane");
+        if (c.valid) write_obs_direct<G>(obs + (row0 + c.lane) * G::OBS, bits);   // (16-B pieces on an aligned tensor)
+    } else if constexpr (G::RAW_SPAN_LEN > 0) {
         static_assert(G::OBS_DIRECT && !G::RAW_OBS && G::OBS >= 32, "mixed rows are stored by their own lane");
         if (c.valid) write_obs_mixed<G>(obs + (row0 + c.lane) * G::OBS, bits);
     } else if constexpr (G::OBS_DIRECT && G::OBS % 16 != 0) {
@@ -258,6 +283,12 @@ template <class G>
 __device__ __forceinline__ void write_obs_direct(uint8_t* o, const uint32_t (&bits)[G::NB])
 {
     if constexpr (G::RAW_SPAN_LEN > 0) {   // (mixed rows, any alignment: a byte loop; the compiler merges neighbours)
+        if constexpr (G::OBS % 16 == 0) {
+            if ((((uintptr_t)o) & 15u) == 0) {
+                write_obs_mixed16<G>(o, bits);
+                return;
+            }
+        }
 #pragma unroll
         for (int j = 0; j < (G::OBS + 3) / 4; j++) {
             const uint32_t v = mixed_dword<G>(bits, j);
@@ -294,6 +325,14 @@ __device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, const Le
     for (int k = 0; k < 8; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg.lo >> (8 * k)));
 #pragma unroll
     for (int k = 8; k < G::LB; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg.hi >> (8 * (k - 8))));
+}
+
+template <class G>
+__device__ __forceinline__ void emit_legal(uint8_t* legal, int64_t row, const Legal256& lg)
+{
+    static_assert(G::LB > 16 && G::LB <= 32, "four-word legal rows");
+#pragma unroll
+    for (int k = 0; k < G::LB; k++) out_store(legal + row * G::LB + k, (uint8_t)(lg.w[k / 8] >> (8 * (k % 8))));
 }
 
 template <class G>
@@ -632,8 +671,9 @@ __global__ __launch_bounds__(BLOCK, G::MIN_WAVES) void k_rollout(RolloutArgs arg
         // slower on every torch allocation, profiles/EXPERIMENTS.md)
         const uint32_t pr = pol.at(seed, genv0, t0 + (uint64_t)t, t == 0);
         int a;
-        static_assert(G::A <= 128, "the policy pick takes a legal mask of one or two 64-bit words");
-        if constexpr (G::A > 64) a = pick_legal128(lg, pr);
+        static_assert(G::A <= 256, "the policy pick takes a legal mask of one, two or four 64-bit words");
+        if constexpr (G::A > 128) a = pick_legal256(lg, pr);
+        else if constexpr (G::A > 64) a = pick_legal128(lg, pr);
         else if constexpr (G::A <= 8) a = pick_legal_small<G::A>((uint32_t)lg, pr);
         else if constexpr (G::A <= 32) a = pick_legal32((uint32_t)lg, pr);
         else a = pick_legal64(lg, pr);
@@ -742,7 +782,10 @@ __global__ __launch_bounds__(BLOCK) void k_policy_actions(const uint32_t* st, in
     g.load(st, n, env);
     int a = -1;
     if (!g.is_over()) {
-        if constexpr (G::A > 64) {
+        if constexpr (G::A > 128) {   // (no game this wide has a rule policy: the ABI refuses any id but CS_POLICY_RANDOM)
+            static_assert(G::MAX_POLICY == 0, "rule policies take masks of at most two words");
+            a = pick_legal256(g.legal(), philox_u32(seed, env_base + (uint64_t)env, t));
+        } else if constexpr (G::A > 64) {
             const Legal128 lg = g.legal();
             const uint32_t pr = philox_u32(seed, env_base + (uint64_t)env, t);
             if constexpr (G::MAX_POLICY > 0) {

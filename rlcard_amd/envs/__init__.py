@@ -1,5 +1,5 @@
 """The env registry: rlcard's plugin API (rlcard/envs/registration.py:8-89, envs/__init__.py) -- register(env_id,
-'module:Class') and make(env_id, config) -- over the engine's nine games. Same ids, same config defaults and the same
+'module:Class') and make(env_id, config) -- over the engine's ten games. Same ids, same config defaults and the same
 ValueError messages for an unknown or a duplicate id."""
 import importlib
 
@@ -37,3 +37,4 @@ register('uno', 'rlcard_amd.envs.uno:UnoEnv')
 register('mahjong', 'rlcard_amd.envs.mahjong:MahjongEnv')
 register('gin-rummy', 'rlcard_amd.envs.gin_rummy:GinRummyEnv')
 register('bridge', 'rlcard_amd.envs.bridge:BridgeEnv')
+register('scout', 'rlcard_amd.envs.scout:ScoutEnv')

@@ -64,6 +64,8 @@ class VecEnv(_abi.Handle):
             raise ValueError('gin-rummy: game_num_players must be 2, got %d' % np_)
         if env_id == 'bridge' and np_ not in (0, 4):
             raise ValueError('bridge: game_num_players must be 4, got %d' % np_)
+        if env_id == 'scout' and np_ not in (0, 4):
+            raise ValueError('scout: game_num_players must be 4, got %d' % np_)
         nd = int(config.get('game_num_decks', -1))
         chips = int(config.get('chips_for_each', 0))
         self.rng_mode = config.get('rng_mode', 'mt19937')   # 'philox': fast, not the reference's deals
