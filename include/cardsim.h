@@ -104,7 +104,7 @@ typedef struct {
  * cs_state_* functions); a consumer built against this header checks cs_abi_version() >= CS_ABI_VERSION before
  * calling cs_game_info_get, which writes sizeof(cs_game_info) bytes of this version. Functions added without a
  * layout change keep the version (cs_rollout_policy, cs_policy_actions, cs_payoff_sums; cs_qnet_values,
- * cs_qnet_actions, the cs_replay_* functions, cs_dqn_targets; cs_pnet_probs, cs_nfsp_scratch_bytes, cs_nfsp_actions,
+ * cs_qnet_actions, the cs_replay_* functions, cs_dqn_targets, cs_dqn_train; cs_pnet_probs, cs_nfsp_scratch_bytes, cs_nfsp_actions,
  * the cs_reservoir_* functions): a consumer that may meet an older library looks the symbol up. */
 #define CS_ABI_VERSION 3
 
@@ -425,6 +425,74 @@ int  cs_replay_gather(cs_replay* r, const int64_t* idx, int64_t B, const cs_repl
 int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* next_legal, const float* reward,
                    const void* done, int64_t B, int32_t num_actions, float gamma, float* target, int32_t* best,
                    void* stream);
+
+/* The DQN learner on the device: K dependent train steps (dqn_agent.py train() and Estimator.update) in one launch of
+ * one workgroup, each step sampling its batch from the replay ring, computing the Double-DQN targets, the train-mode
+ * forward, the backward and the Adam step, in place on the caller's tensors. All pointers DEVICE memory.
+ * The network UNFOLDED (EstimatorNetwork's state_dict): BatchNorm1d over the in_dim inputs, then cs_qnet's stack. */
+typedef struct {
+    int32_t in_dim;        /* = cs_game_info.obs_dim */
+    int32_t num_hidden;    /* 1..4 */
+    int32_t hidden[4];     /* widths, each 1..128 */
+    int32_t num_actions;   /* = cs_game_info.num_actions, <= 64 */
+    int32_t reserved;
+    float* bn_weight;      /* [in_dim] BatchNorm1d.weight, .bias, .running_mean, .running_var */
+    float* bn_bias;
+    float* bn_mean;
+    float* bn_var;
+    int64_t* bn_tracked;   /* [1] num_batches_tracked */
+    float bn_eps, bn_momentum;
+    float* W[5];           /* W[k] [out_k][in_k] row-major, W[num_hidden] = output layer */
+    float* b[5];
+} cs_dqn_net;
+/* torch.optim.Adam's state of the Q-network's parameters (exp_avg m, exp_avg_sq v of each tensor) and its
+ * hyperparameters; step0 = the steps taken so far (state['step']); the launch's step k is Adam step step0 + k + 1. */
+typedef struct {
+    float *bn_weight_m, *bn_weight_v, *bn_bias_m, *bn_bias_v;
+    float* W_m[5];
+    float* W_v[5];
+    float* b_m[5];
+    float* b_v[5];
+    double lr, beta1, beta2, eps;
+    int64_t step0;
+} cs_dqn_adam;
+typedef struct {
+    int32_t K;             /* train steps of the launch, 1..4096 */
+    int32_t B;             /* batch size, 2..64 */
+    float gamma;           /* discount factor */
+    int32_t reserved;
+    uint64_t seed;         /* key of the sampler */
+    uint64_t train_t0;     /* train_t of step 0 (the sampler's counter and the target-copy schedule) */
+    int64_t target_every;  /* > 0: after the update of a step with train_t % target_every == 0 the Q-network's
+                              state_dict is copied into the target network's; 0: never */
+    const int64_t* idx;    /* i64 [K][B] or NULL: the batches' indices (cs_replay_gather's meaning, clamped alike) */
+    float* loss;           /* f32 [K] the steps' losses */
+    int64_t* idx_out;      /* i64 [K][B] or NULL: the indices used */
+    float* target_out;     /* f32 [K][B] or NULL: the targets y */
+    float* grads;          /* f32 or NULL: the gradients of the launch's last step, flat, in the order bn_weight, bn_bias,
+                              W[0], b[0], W[1], b[1], ... (EstimatorNetwork.parameters()) */
+} cs_dqn_train_args;
+/* Step k (train_t = train_t0 + k) of the launch, restating train():
+ *   indices  idx[k], or B distinct slots drawn uniformly from the size = min(total, capacity) transitions held, by
+ *            Floyd's algorithm: for i = 0 .. B-1, j = size - B + i, r = (x * (j + 1)) >> 64 with x = w[0] | w[1] << 32
+ *            of Philox keyed by seed on the counter (train_t, i); the i-th index is r, or j where r is already taken.
+ *   targets  eval-mode forwards (BatchNorm on its running statistics) of next_state through qnet and target, then
+ *            cs_dqn_targets' line.
+ *   update   train-mode forward of state (BatchNorm on the batch's mean and biased variance; running_mean / running_var
+ *            move by bn_momentum, the latter towards the unbiased variance; num_batches_tracked += 1), loss = mean
+ *            (Q[b][action_b] - y_b)^2, backward through the step's old weights, Adam on every parameter: m += (1 -
+ *            beta1)(g - m), v = beta2 v + (1 - beta2) g^2, p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) +
+ *            eps), the two bias corrections formed in fp64.
+ * Everything is fp32 with fixed summation orders: the result is a function of the arguments alone, bit for bit, and
+ * K steps in one launch leave what K launches of one step leave. Nothing is read back: the call returns once the
+ * launch is queued, except that the form without idx reads the ring's total once (synchronously) while the ring is not
+ * yet known to hold B transitions.
+ * Refusals: null or out-of-range descriptors (cs_qnet's ranges; target's dims must be qnet's; in_dim / num_actions the
+ * ring's game's), B outside 2..64, K outside 1..4096 CS_E_INVALID; a net whose step needs more than the 160 KiB of
+ * LDS a workgroup can have CS_E_UNSUPPORTED (no game of at most 64 actions there is: 816 obs bytes, B = 64 and four
+ * layers of 128 fit); fewer than B transitions held, in the form without idx, CS_E_STATE. */
+int cs_dqn_train(cs_replay* r, const cs_dqn_net* qnet, const cs_dqn_net* target, const cs_dqn_adam* opt,
+                 const cs_dqn_train_args* args, void* stream);
 
 /* ---- NFSP agent (rlcard/agents/nfsp_agent.py) -------------------------------------------------------------------
  * The average-policy network is a cs_qnet descriptor read as Linear/ReLU (AveragePolicyNetwork with its BatchNorm

@@ -72,6 +72,26 @@ class ReplayBatch(C.Structure):
                 ('next_legal', C.c_void_p), ('done', C.c_void_p)]
 
 
+class DqnNet(C.Structure):   # cs_dqn_net: the unfolded Q-network cs_dqn_train updates in place
+    _fields_ = [('in_dim', C.c_int32), ('num_hidden', C.c_int32), ('hidden', C.c_int32 * 4),
+                ('num_actions', C.c_int32), ('reserved', C.c_int32), ('bn_weight', C.c_void_p),
+                ('bn_bias', C.c_void_p), ('bn_mean', C.c_void_p), ('bn_var', C.c_void_p), ('bn_tracked', C.c_void_p),
+                ('bn_eps', C.c_float), ('bn_momentum', C.c_float), ('W', C.c_void_p * 5), ('b', C.c_void_p * 5)]
+
+
+class DqnAdam(C.Structure):   # cs_dqn_adam: torch.optim.Adam's state of those parameters and its hyperparameters
+    _fields_ = [('bn_weight_m', C.c_void_p), ('bn_weight_v', C.c_void_p), ('bn_bias_m', C.c_void_p),
+                ('bn_bias_v', C.c_void_p), ('W_m', C.c_void_p * 5), ('W_v', C.c_void_p * 5), ('b_m', C.c_void_p * 5),
+                ('b_v', C.c_void_p * 5), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double),
+                ('eps', C.c_double), ('step0', C.c_int64)]
+
+
+class DqnTrainArgs(C.Structure):   # cs_dqn_train_args
+    _fields_ = [('K', C.c_int32), ('B', C.c_int32), ('gamma', C.c_float), ('reserved', C.c_int32),
+                ('seed', C.c_uint64), ('train_t0', C.c_uint64), ('target_every', C.c_int64), ('idx', C.c_void_p),
+                ('loss', C.c_void_p), ('idx_out', C.c_void_p), ('target_out', C.c_void_p), ('grads', C.c_void_p)]
+
+
 def _prototypes():
     vp, i32, i64, u32, u64, f32, rc, P = (C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_int,
                                           C.POINTER)
@@ -112,6 +132,7 @@ def _prototypes():
         'cs_replay_size': (rc, [vp, vp, vp]),
         'cs_replay_gather': (rc, [vp, vp, i64, P(ReplayBatch), vp]),
         'cs_dqn_targets': (rc, [vp, vp, vp, vp, vp, i64, i32, f32, vp, vp, vp]),
+        'cs_dqn_train': (rc, [vp, P(DqnNet), P(DqnNet), P(DqnAdam), P(DqnTrainArgs), vp]),
         'cs_pnet_probs': (rc, [vp, net, vp, vp, i64, vp, vp]),
         'cs_nfsp_scratch_bytes': (i64, [i64]),
         'cs_nfsp_actions': (rc, [vp, net, net, vp, vp, vp, vp, i64, f32, u64, u64, u64, vp, vp, vp, vp]),

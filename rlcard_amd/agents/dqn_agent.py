@@ -9,6 +9,7 @@
     DeviceMemory         cs_replay: the replay FIFO in HBM, filled from rollout-layout trajectories (reorganize on the
                          device, with the transitions that straddle two windows carried, not dropped)
     DQNAgent.feed_vec / train   targets from cs_dqn_targets; forward / backward / Adam stay torch
+    DQNAgent.train_fused cs_dqn_train: whole train steps on the device, many per launch (feed_vec(..., fused=True))
     DQNCollector         the acting loop (the DMCActor pattern): the agent's seats by step_vec, the others by an engine
                          policy, recorded into a trajectory with final observations
 """
@@ -303,6 +304,9 @@ def dqn_targets(q_next, q_next_target, next_legal, reward, done, gamma):
     return target, best
 
 
+FUSED_MAX_STEPS = 4096   # train steps of one cs_dqn_train launch
+
+
 class DQNAgent:
     """rlcard's DQNAgent (constructor arguments and methods), plus attach() and the *_vec methods for a VecEnv."""
 
@@ -333,6 +337,7 @@ class DQNAgent:
         self.vec = None
         self.generator = None    # torch.Generator of DeviceMemory.sample (None: torch's global one)
         self.last_loss = None
+        self.train_seed = 0      # key of train_fused's sampler (the draws are keyed by (train_seed, train_t))
         self.save_path = save_path
         self.save_every = save_every
 
@@ -470,10 +475,11 @@ class DQNAgent:
         first += (-(first - self.replay_memory_init_size)) % e
         return 0 if first > t1 else (t1 - first) // e + 1
 
-    def feed_vec(self, traj, seats, train_steps=None):
+    def feed_vec(self, traj, seats, train_steps=None, fused=False):
         """Push the seats' transitions of a trajectory into the device memory, advance total_t by the number
         appended, and train as often as feed would have over that advance (or exactly train_steps times) -> the
-        losses."""
+        losses. fused: the steps run on the device (train_fused, in launches of at most FUSED_MAX_STEPS), and the
+        losses come back as one float32 device tensor."""
         mem = self.device_memory
         before = mem.total
         mem.push(traj, seats)
@@ -481,7 +487,121 @@ class DQNAgent:
         t0 = self.total_t
         self.total_t += fresh
         n = self.train_steps_for(t0, self.total_t) if train_steps is None else int(train_steps)
-        return [self.train() for _ in range(n)]
+        if not fused:
+            return [self.train() for _ in range(n)]
+        losses = [self.train_fused(min(FUSED_MAX_STEPS, n - k)) for k in range(0, n, FUSED_MAX_STEPS)]
+        return torch.cat(losses) if losses else torch.empty(0, dtype=torch.float32, device=self.device)
+
+    # -- the learner on the device -------------------------------------------------------------------------------------
+    def _adam_state(self):
+        """The Q-network's optimizer as cs_dqn_train takes it: (the param group, the state dict per parameter in
+        parameters() order), the state created as Adam's first step would create it where there is none yet."""
+        opt = self.q_estimator.optimizer
+        if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
+            raise ValueError('train_fused takes torch.optim.Adam with one parameter group, got %s' % type(opt).__name__)
+        g = opt.param_groups[0]
+        for flag in ('weight_decay', 'amsgrad', 'maximize', 'capturable', 'fused'):
+            if g.get(flag):
+                raise ValueError('train_fused takes plain Adam: %s=%r is not supported' % (flag, g[flag]))
+        states = []
+        for p in self.q_estimator.qnet.parameters():
+            st = opt.state[p]
+            if len(st) == 0:
+                st['step'] = torch.zeros((), dtype=torch.float32, device='cpu')
+                st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            states.append(st)
+        return g, states
+
+    @staticmethod
+    def _dqn_net(est, keep):
+        """cs_dqn_net of an Estimator's network (the tensors are torch's own; `keep` holds them past the call)"""
+        fc = est.qnet.fc_layers
+        bn, linears = fc[1], [m for m in fc if isinstance(m, nn.Linear)]
+        if not 1 <= len(linears) - 1 <= 4:
+            raise ValueError('the train kernel takes 1..4 hidden layers, got %d' % (len(linears) - 1))
+        if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+            raise ValueError('train_fused takes an affine BatchNorm1d with running statistics and a momentum')
+        net = _abi.DqnNet()
+        net.in_dim, net.num_hidden, net.num_actions = bn.num_features, len(linears) - 1, linears[-1].out_features
+        tensors = [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked]
+        net.bn_weight, net.bn_bias, net.bn_mean, net.bn_var, net.bn_tracked = (t.data_ptr() for t in tensors)
+        net.bn_eps, net.bn_momentum = bn.eps, bn.momentum
+        for k, m in enumerate(linears):
+            if k < net.num_hidden:
+                net.hidden[k] = m.out_features
+            net.W[k], net.b[k] = m.weight.data_ptr(), m.bias.data_ptr()
+            tensors += [m.weight, m.bias]
+        for t in tensors:
+            if not t.is_cuda or t.device != bn.weight.device or not t.is_contiguous() or \
+                    t.dtype != (torch.int64 if t is bn.num_batches_tracked else torch.float32):
+                raise ValueError('train_fused takes contiguous float32 parameters on the env\'s device')
+        keep += tensors
+        return net
+
+    def train_fused(self, steps, idx=None, debug=False):
+        """`steps` train() calls in one kernel launch (cs_dqn_train: sampling, targets, forward, backward and Adam of
+        every step on the device, in place on the networks' and the optimizer's tensors) -> the losses, a float32
+        device tensor [steps]; nothing waits for the device. The batches are drawn by the kernel's own sampler, keyed by
+        (train_seed, train_t), not by `generator`; idx (int64 [steps, batch_size]) gives them instead. debug: also the
+        indices used (int64 [steps, B]), the targets (float32 [steps, B]) and the last step's gradients (float32, flat,
+        in qnet.parameters() order)."""
+        if self.device_memory is None or self.vec is None:
+            raise _abi.CardsimError('DQNAgent.attach(vec) comes before train_fused')
+        steps, B = int(steps), int(self.batch_size)
+        group, states = self._adam_state()
+        keep = []
+        qnet = self._dqn_net(self.q_estimator, keep)
+        tnet = self._dqn_net(self.target_estimator, keep)
+        d = keep[0].device
+        ad = _abi.DqnAdam()
+        names = [('bn_weight', None), ('bn_bias', None)] + [(w, k) for k in range(qnet.num_hidden + 1)
+                                                            for w in ('W', 'b')]
+        for (name, k), st in zip(names, states):
+            m, v = st['exp_avg'], st['exp_avg_sq']
+            if m.device != d or not m.is_contiguous() or not v.is_contiguous():
+                raise ValueError('train_fused: Adam\'s state is not on the env\'s device')
+            if k is None:
+                setattr(ad, name + '_m', m.data_ptr())
+                setattr(ad, name + '_v', v.data_ptr())
+            else:
+                getattr(ad, name + '_m')[k] = m.data_ptr()
+                getattr(ad, name + '_v')[k] = v.data_ptr()
+        ad.lr, ad.eps = float(group['lr']), float(group['eps'])
+        ad.beta1, ad.beta2 = (float(x) for x in group['betas'])
+        ad.step0 = int(float(states[0]['step']))
+        args = _abi.DqnTrainArgs()
+        args.K, args.B, args.gamma = steps, B, float(self.discount_factor)
+        args.seed, args.train_t0 = int(self.train_seed) & (2 ** 64 - 1), int(self.train_t)
+        every = self.update_target_estimator_every
+        args.target_every = int(every) if every and every != float('inf') else 0
+        loss = torch.empty(max(steps, 0), dtype=torch.float32, device=d)
+        out = None
+        if idx is not None:
+            idx = torch.as_tensor(idx, device=d).to(torch.int64).contiguous()
+            if tuple(idx.shape) != (steps, B):
+                raise ValueError('train_fused: idx must be [steps, batch_size]')
+            args.idx = idx.data_ptr()
+        if debug:
+            n_par = sum(p.numel() for p in self.q_estimator.qnet.parameters())
+            out = (torch.empty((max(steps, 0), B), dtype=torch.int64, device=d),
+                   torch.empty((max(steps, 0), B), dtype=torch.float32, device=d),
+                   torch.empty(n_par, dtype=torch.float32, device=d))
+            args.idx_out, args.target_out, args.grads = (t.data_ptr() for t in out)
+        args.loss = loss.data_ptr()
+        _abi.call('cs_dqn_train', self.device_memory._h, C.byref(qnet), C.byref(tnet), C.byref(ad), C.byref(args),
+                  self.vec._stream(), device=d)
+        # the kernel wrote behind torch's version counters: the host-side counters and caches follow by hand
+        for st in states:
+            st['step'] += steps
+        before = self.train_t
+        self.train_t += steps
+        self.q_estimator._folded = None
+        self.target_estimator._folded = None
+        self.last_loss = loss[-1]
+        if self.save_path and self.train_t // self.save_every != before // self.save_every:
+            self.save_checkpoint(self.save_path)
+        return (loss,) + out if debug else loss
 
     # -- checkpoints ---------------------------------------------------------------------------------------------------
     def checkpoint_attributes(self):
@@ -594,6 +714,6 @@ class DQNCollector:
     def _stepped(self, state):
         """after every env step, with the state it led to (NFSPCollector resamples the finished games' modes)"""
 
-    def run(self, train_steps=None):
-        """collect() + agent.feed_vec -> the losses of the train steps."""
-        return self.agent.feed_vec(self.collect(), self.seats, train_steps)
+    def run(self, train_steps=None, fused=False):
+        """collect() + agent.feed_vec -> the losses of the train steps (fused: on the device, as a tensor)."""
+        return self.agent.feed_vec(self.collect(), self.seats, train_steps, fused)

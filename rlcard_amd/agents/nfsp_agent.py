@@ -414,14 +414,15 @@ class NFSPAgent:
         e = self._train_every
         return max(0, t1 // e - t0 // e)
 
-    def feed_vec(self, traj, mode_rows, seats, train_steps=None, sl_steps=None):
+    def feed_vec(self, traj, mode_rows, seats, train_steps=None, sl_steps=None, fused=False):
         """The inner DQNAgent.feed_vec (push, train), then the trajectory's best-response rows of `seats` into the
         reservoir; total_t advances by the transitions the replay memory took, and train_sl runs as often as feed
         would have run it over that advance, with the reservoir as the push left it (or exactly sl_steps times)
-        -> (the DQN losses, the average-policy losses)."""
+        -> (the DQN losses, the average-policy losses). fused: the inner agent's steps run on the device
+        (DQNAgent.train_fused); train_sl stays torch."""
         rl = self._rl_agent
         t_rl = rl.total_t
-        rl_losses = rl.feed_vec(traj, seats, train_steps)
+        rl_losses = rl.feed_vec(traj, seats, train_steps, fused)
         self.device_reservoir.push(traj, mode_rows, seats)
         t0 = self.total_t
         self.total_t += rl.total_t - t_rl
@@ -502,6 +503,6 @@ class NFSPCollector(DQNCollector):
     def _stepped(self, state):
         self.agent.sample_episode_policy_vec(state['done'], self.t, self.seed)
 
-    def run(self, train_steps=None, sl_steps=None):
+    def run(self, train_steps=None, sl_steps=None, fused=False):
         """collect() + agent.feed_vec -> (the DQN losses, the average-policy losses)."""
-        return self.agent.feed_vec(self.collect(), self.mode_rows, self.seats, train_steps, sl_steps)
+        return self.agent.feed_vec(self.collect(), self.mode_rows, self.seats, train_steps, sl_steps, fused)

@@ -516,6 +516,7 @@ int cs_qnet_actions(cs_handle* h, const cs_qnet* net, const void* obs, const voi
 
 struct cs_replay : cs_sub {   // mem: the ring, the pending store and the counter; scratch: i32 [2][entries], code and
     cs::ReplayRing r;         // pos of a push
+    int64_t seen_total = 0;   // cs_dqn_train: the ring's total as last read (it only grows)
 };
 
 int cs_replay_create(cs_handle* h, int64_t capacity, cs_replay** out)
@@ -612,6 +613,62 @@ int cs_dqn_targets(const float* q_next, const float* q_next_target, const void* 
     if (B == 0) return CS_OK;
     return ::done(cs::launch_dqn_targets(q_next, q_next_target, (const uint8_t*)next_legal, reward, (const uint8_t*)done,
                                          B, num_actions, gamma, target, best, (hipStream_t)stream), "cs_dqn_targets");
+}
+
+static int dqn_net_check(const cs_replay* r, const cs_dqn_net* n)
+{
+    const cs_game_info& info = r->h->ops->info;
+    if (n->in_dim != info.obs_dim || n->num_actions != info.num_actions)
+        return fail(CS_E_INVALID, "cs_dqn_net: in_dim / num_actions are not the ring's game's");
+    if (n->num_hidden < 1 || n->num_hidden > CS_QNET_MAX_HIDDEN)
+        return fail(CS_E_INVALID, "cs_dqn_net: num_hidden must be 1..4");
+    for (int l = 0; l <= n->num_hidden; l++) {
+        if (l < n->num_hidden && (n->hidden[l] < 1 || n->hidden[l] > CS_QNET_MAX_WIDTH))
+            return fail(CS_E_INVALID, "cs_dqn_net: hidden widths must be 1..128");
+        if (!n->W[l] || !n->b[l]) return fail(CS_E_INVALID, "cs_dqn_net: null weights");
+    }
+    if (!n->bn_weight || !n->bn_bias || !n->bn_mean || !n->bn_var || !n->bn_tracked)
+        return fail(CS_E_INVALID, "cs_dqn_net: null BatchNorm tensors");
+    if (!(n->bn_eps > 0.f) || !(n->bn_momentum >= 0.f && n->bn_momentum <= 1.f))
+        return fail(CS_E_INVALID, "cs_dqn_net: BatchNorm eps must be positive and momentum in [0, 1]");
+    return CS_OK;
+}
+
+int cs_dqn_train(cs_replay* r, const cs_dqn_net* qnet, const cs_dqn_net* target, const cs_dqn_adam* opt,
+                 const cs_dqn_train_args* args, void* stream)
+{
+    if (!r || !qnet || !target || !opt || !args) return fail(CS_E_INVALID, "null argument");
+    if (args->B < 2 || args->B > 64) return fail(CS_E_INVALID, "cs_dqn_train: B must be 2..64");
+    if (args->K < 1 || args->K > 4096) return fail(CS_E_INVALID, "cs_dqn_train: K must be 1..4096");
+    if (!args->loss) return fail(CS_E_INVALID, "cs_dqn_train: null loss buffer");
+    if (args->target_every < 0) return fail(CS_E_INVALID, "cs_dqn_train: target_every must not be negative");
+    int rc = dqn_net_check(r, qnet);
+    if (rc != CS_OK) return rc;
+    if ((rc = dqn_net_check(r, target)) != CS_OK) return rc;
+    if (target->num_hidden != qnet->num_hidden) return fail(CS_E_INVALID, "cs_dqn_train: the networks' shapes differ");
+    for (int l = 0; l < qnet->num_hidden; l++)
+        if (target->hidden[l] != qnet->hidden[l])
+            return fail(CS_E_INVALID, "cs_dqn_train: the networks' shapes differ");
+    if (!opt->bn_weight_m || !opt->bn_weight_v || !opt->bn_bias_m || !opt->bn_bias_v)
+        return fail(CS_E_INVALID, "cs_dqn_adam: null state");
+    for (int l = 0; l <= qnet->num_hidden; l++)
+        if (!opt->W_m[l] || !opt->W_v[l] || !opt->b_m[l] || !opt->b_v[l])
+            return fail(CS_E_INVALID, "cs_dqn_adam: null state");
+    if (!(opt->lr >= 0.0) || !(opt->beta1 >= 0.0 && opt->beta1 < 1.0) || !(opt->beta2 >= 0.0 && opt->beta2 < 1.0) ||
+        !(opt->eps >= 0.0) || opt->step0 < 0)
+        return fail(CS_E_INVALID, "cs_dqn_adam: lr, eps >= 0, betas in [0, 1) and step0 >= 0");
+    if (cs::dqn_train_lds_bytes(*qnet, args->B) > 160 * 1024)
+        return fail(CS_E_UNSUPPORTED, "cs_dqn_train: the step needs more than the 160 KiB of LDS a workgroup can have");
+    if ((rc = set_device(r->h)) != CS_OK) return rc;
+    if (!args->idx && r->seen_total < args->B) {   // (once the ring is known to hold B transitions it always does)
+        int64_t t = 0;
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(&t, r->r.total, sizeof(int64_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail_hip(e, "cs_dqn_train");
+        r->seen_total = t;
+        if (t < args->B) return fail(CS_E_STATE, "cs_dqn_train: the memory holds fewer than B transitions");
+    }
+    return done(cs::launch_dqn_train(r->r, *qnet, *target, *opt, *args, (hipStream_t)stream), "cs_dqn_train");
 }
 
 // ---- NFSP ---------------------------------------------------------------------------------------------------------

@@ -65,4 +65,9 @@ hipError_t launch_dqn_targets(const float* q_next, const float* q_next_target, c
                               const float* reward, const uint8_t* done, int64_t B, int32_t A, float gamma,
                               float* target, int32_t* best, hipStream_t s);
 
+// cs_dqn_train.hip: dynamic LDS bytes of the one k_dqn_train workgroup for this net at batch size B
+int64_t dqn_train_lds_bytes(const cs_dqn_net& net, int32_t B);
+hipError_t launch_dqn_train(const ReplayRing& r, const cs_dqn_net& qnet, const cs_dqn_net& target,
+                            const cs_dqn_adam& opt, const cs_dqn_train_args& args, hipStream_t s);
+
 }  // namespace cs

@@ -246,6 +246,12 @@ static void abi_host_agents()
     EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, 1, 0, 0.9f, &f, &i32, nullptr) == CS_E_INVALID);
     EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, -1, 4, 0.9f, &f, &i32, nullptr) == CS_E_INVALID);
     EXPECT(cs_dqn_targets(&f, &f, &u8, &f, &u8, 0, 4, 0.9f, &f, &i32, nullptr) == CS_OK);
+    {
+        cs_dqn_net dn = {};
+        cs_dqn_adam da = {};
+        cs_dqn_train_args dt = {};
+        EXPECT(cs_dqn_train(nullptr, &dn, &dn, &da, &dt, nullptr) == CS_E_INVALID);
+    }
     cs_replay_destroy(nullptr);
 
     EXPECT(cs_pnet_probs(nullptr, &net, &u8, &u8, 1, &f, nullptr) == CS_E_INVALID);
