@@ -374,9 +374,9 @@ typedef struct {
  * bytes read as one little-endian word (UNO: 8 bytes, 61 bits); bits from num_actions up are ignored. Refusals (both
  * functions): a game with more than 64 actions CS_E_UNSUPPORTED (DouDizhu); in_dim / num_actions not the handle's
  * game's, widths or layer counts out of range, null weights CS_E_INVALID. Every descriptor within those ranges runs on
- * every game of at most 64 actions there is (a block of 64 rows needs 74 240 B of LDS at most: a game of more than 8
- * actions or 128 obs bytes keeps its obs rows as bytes); a net that needed more than the 160 KiB a block can have --
- * only a game with some 1 700 obs bytes could -- would be CS_E_UNSUPPORTED. */
+ * every game of at most 64 actions there is (a block of 64 rows needs 100 352 B of LDS at most, on Mahjong: a game of
+ * more than 8 actions or 128 obs bytes keeps its obs rows as bytes); a net that needed more than the 160 KiB a block
+ * can have -- only a game with some 1 700 obs bytes could -- would be CS_E_UNSUPPORTED. */
 int cs_qnet_values(cs_handle* h, const cs_qnet* net, const void* obs, const void* legal, int64_t rows, float* q,
                    void* stream);
 /* DQNAgent.step / eval_step for `rows` rows: actions i32 [rows] = the first maximum of the row's Q-values among its

@@ -481,8 +481,9 @@ static int qnet_check(const cs_handle* h, const cs_qnet* net, const void* obs, i
             return fail(CS_E_INVALID, "cs_qnet: hidden widths must be 1..128");
         if (!net->W[l] || !net->b[l]) return fail(CS_E_INVALID, "cs_qnet: null weights");
     }
-    // (every descriptor the checks above pass needs 74 240 B at most on the games there are: two 128-unit buffers and
-    // two weight tiles, the obs of a wide game being bytes inside the first buffer; this guards a future game's obs)
+    // (every descriptor the checks above pass needs 100 352 B at most on the games there are -- qnet_lds_bytes of
+    // Mahjong with two 128-unit layers: the 816 x 72 obs bytes make the first buffer 230 units, the second holds 128,
+    // (230 + 128) x 256 B, plus two weight tiles of 4 352 B; this guards a future game's obs)
     if (cs::qnet_lds_bytes(*net) > 160 * 1024)
         return fail(CS_E_UNSUPPORTED, "cs_qnet: the net needs more than the 160 KiB of LDS a block can have");
     if (rows < 0 || rows > 0x7FFFFFFF) return fail(CS_E_INVALID, "rows out of range");

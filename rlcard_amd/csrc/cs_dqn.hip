@@ -482,7 +482,7 @@ static hipError_t launch_net(const cs_qnet& net, const uint8_t* obs, const uint8
     qnet_sizes(net, &szA, &szB);
     const int64_t bytes = qnet_lds_bytes(net);
     auto kern = qnet_wide(net) ? k_qnet<ACT, HEAD, LIST, true> : k_qnet<ACT, HEAD, LIST, false>;
-    if (bytes > 65536) {   // past the default limit of dynamic LDS (the [128, 128, ..] nets): raise this kernel's
+    if (bytes > 65536) {   // past the default limit of dynamic LDS (the [128, 128, ..] nets, any on Mahjong): raise it
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
     }

@@ -20,7 +20,11 @@ CASES = {'leduc': ('leduc-holdem', 256, [64, 64], 32),       # the default
          'b64': ('leduc-holdem', 256, [64, 64], 64),         # the largest batch
          'uno': ('uno', 256, [128, 128], 32),                # byte obs of 240, 61 actions, 8 mask bytes
          'mahjong': ('mahjong', 65, [64], 32),               # 816 obs bytes: one column per thread, no output groups
-         'widest': ('mahjong', 65, [128, 128, 128, 128], 64)}   # the most LDS a game there is needs: 156 416 B
+         'widest': ('mahjong', 65, [128, 128, 128, 128], 64),   # the most LDS a game there is needs: 156 416 B
+         # obs rows that are no whole dwords: the byte-wise gather and the first layer's scalar k loop
+         'nolimit': ('no-limit-holdem', 256, [64, 64], 32),  # 54 obs bytes, 5 actions: 18 output groups, 972 threads
+         'blackjack': ('blackjack', 256, [128], 32),         # 2 raw obs bytes up to about 30, 2 actions, one seat
+         'limit': ('limit-holdem', 256, [20], 5)}            # 72 obs bytes in 14 uneven output groups, 8 padded rows
 ALL = list(CASES)
 
 
@@ -177,12 +181,10 @@ def test_sampler_draws_a_full_memory_whole():
 
 
 # ---- 2. targets ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('name', ALL)
-def test_targets(name):
+def check_targets(agent, name, both_done=False):
     """target_out of a launch's first step (the networks as they were before it) against the fp64 eval forwards and
     the target line. Every row of the seeded cases is clear: the fp64 top-two gap of q_next over the legal actions
-    exceeds 16 E_torch (rows with fewer than two legal actions have nothing to confuse)."""
-    agent = new_agent(name)
+    exceeds 16 E_torch (rows with fewer than two legal actions have nothing to confuse). -> the two steps' indices"""
     agent.train_t = 5
     q_state, t_state = state_of(agent.q_estimator), state_of(agent.target_estimator)
     _, idx, y, _ = agent.train_fused(2, debug=True)
@@ -199,8 +201,14 @@ def test_targets(name):
     check_bound(got.numpy(), y64.numpy(), y32.numpy(), name + ' targets')
     dn = b['done'].bool()
     assert torch.equal(got[dn], b['reward'][dn])                       # a terminal row: exactly the reward
-    if name in ('leduc', 'b64'):
+    if both_done:                                                      # (terminal and non-terminal rows)
         assert dn.any() and not dn.all()
+    return idx.cpu().numpy()
+
+
+@pytest.mark.parametrize('name', ALL)
+def test_targets(name):
+    check_targets(new_agent(name), name, both_done=name in ('leduc', 'b64'))
 
 
 # ---- 3. gradients ----------------------------------------------------------------------------------------------------
@@ -215,8 +223,7 @@ def ref_update(agent, q_state, b, y, dtype):
     return loss.detach(), [p.grad for p in net.parameters()], net
 
 
-@pytest.mark.parametrize('name', ALL)
-def test_gradients(name):
+def check_gradients(agent, name, zero_bias):
     """K = 1: the gradients, the loss and BatchNorm's running statistics against fp64 autograd of the train-mode
     EstimatorNetwork on the same batch, with the kernel's own target_out as the constant target (so that an argmax
     near-tie cannot leak in).
@@ -224,8 +231,6 @@ def test_gradients(name):
     beta_k * db_0[o] -- exactly zero where beta_k is zero, which is how a fresh network starts; the 'leduc' case keeps
     BatchNorm's bias at zero and asserts the exact zeros, the other cases have a random bias and those columns fall
     under the bound like every other."""
-    zero_bias = name == 'leduc'
-    agent = new_agent(name, bn_bias=not zero_bias)
     agent.train_t = 5
     q_state = state_of(agent.q_estimator)
     tracked = int(q_state['fc_layers.1.num_batches_tracked'])
@@ -257,21 +262,60 @@ def test_gradients(name):
     assert after['fc_layers.1.num_batches_tracked'].dtype == torch.int64
 
 
+@pytest.mark.parametrize('name', ALL)
+def test_gradients(name):
+    zero_bias = name == 'leduc'
+    check_gradients(new_agent(name, bn_bias=not zero_bias), name, zero_bias)
+
+
+# ---- 3b. a wrapped ring, given indices out of range --------------------------------------------------------------------
+@pytest.mark.parametrize('cap', [97, 1000])
+def test_wrapped_ring(cap):
+    """A capacity under the 'leduc' rollout's 3 850 transitions: the ring has wrapped and its oldest transition is not
+    in slot 0, so slot = (total - size + pick) % cap is no identity and no permutation of one batch (the cap = 32 tests
+    above cannot tell a wrong slot). The sampler draws from cap; the targets and the gradients are test_targets' and
+    test_gradients' against gather() on the same ring, which test_gpu_dqn.py's 'leduc-grow' case holds to RefReplay
+    wrapped. The last 97 transitions of a 16-step window are all terminal (a row whose game goes on waits for the next
+    push), so that ring checks slots, states, actions and rewards; 1000 has rows of both kinds, as 'leduc' asserts."""
+    agent = new_agent('leduc', cap=cap)
+    size, total = agent.device_memory.sizes()
+    print('wrapped ring: size %d total %d, oldest in slot %d' % (size, total, total % cap))
+    assert total > cap and size == cap and total % cap != 0
+    agent.train_seed = 2 ** 40 + 3
+    idx = check_targets(agent, 'leduc cap %d' % cap, both_done=cap == 1000)
+    assert np.array_equal(idx, floyd_batches(2 ** 40 + 3, [5, 6], cap, 32))
+    check_gradients(new_agent('leduc', cap=cap, bn_bias=False), 'leduc cap %d' % cap, True)
+
+
+def test_given_indices_are_clamped():
+    """idx entries outside [0, size) are the caller's error and are clamped: idx_out shows 0 and size - 1, and the
+    step is the one a twin agent makes on the clamped indices, bit for bit."""
+    first, second = new_agent('leduc'), new_agent('leduc')
+    size, B = len(first.device_memory), first.batch_size
+    good = floyd_batches(11, [0, 1], size, B)
+    bad = good.copy()
+    bad[0, 3], bad[1, B - 1] = -5, size + 3
+    good[0, 3], good[1, B - 1] = 0, size - 1
+    _, idx_out, _, _ = first.train_fused(2, idx=torch.from_numpy(bad), debug=True)
+    assert np.array_equal(idx_out.cpu().numpy(), good)
+    second.train_fused(2, idx=torch.from_numpy(good))
+    assert same(everything(first), everything(second))
+    assert not same(everything(first)[:4], everything(new_agent('leduc'))[:4])
+
+
 # ---- 4. Adam ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('name', ['leduc', 'odd', 'uno'])
-def test_adam_exactly(name):
-    """Three consecutive K = 1 calls from a fresh optimizer (t = 1, 2, 3), each checked from the kernel's own fp32
-    gradient g and the m0, v0, p0 read before the call, with u = 2^-24:
+def check_adam(agent, ts, lr):
+    """Consecutive K = 1 calls at Adam's steps ts, each checked from the kernel's own fp32 gradient g and the m0, v0,
+    p0 read before the call, with u = 2^-24:
       m1 = m0 + (1 - beta1)(g - m0): three roundings and the constant's        -> |m1 - m64| <= 5 u max(|m0|, |g|)
       v1 = beta2 v0 + (1 - beta2) g^2: four roundings and the constants'       -> |v1 - v64| <= 6 u max(v0, g^2)
       p1 = p0 - Delta, Delta = step * m1 / (sqrt(v1) * rbc2 + eps) from fp64 bias corrections: the kernel rounds the
       two constants step and rbc2 = 1 / sqrt(1 - beta2^t), sqrt, the denominator's FMA, the product and the quotient:
       six roundings in Delta and one in the subtraction, doubled                -> |p1 - (p0 - Delta64)| <= 2 u |p1| +
       8 u |Delta64|, Delta64 formed in fp64 from the kernel's m1, v1."""
-    lr, b1, b2, eps, u = 1e-3, 0.9, 0.999, 1e-8, 2.0 ** -24
-    agent = new_agent(name, lr=lr, adam='fresh')
+    b1, b2, eps, u = 0.9, 0.999, 1e-8, 2.0 ** -24
     agent.train_t = 5
-    for t in (1, 2, 3):
+    for t in ts:
         agent._adam_state()
         p0 = [p.detach().cpu().double() for p in agent.q_estimator.qnet.parameters()]
         mv0 = adam_of(agent)
@@ -293,8 +337,23 @@ def test_adam_exactly(name):
         assert steps == {t}
 
 
+@pytest.mark.parametrize('name', ['leduc', 'odd', 'uno', 'nolimit', 'blackjack', 'limit'])
+def test_adam_exactly(name):
+    """from a fresh optimizer: t = 1, 2, 3"""
+    check_adam(new_agent(name, lr=1e-3, adam='fresh'), (1, 2, 3), 1e-3)
+
+
+def test_adam_far_from_step_one():
+    """Seeded moments and step 999 999, so the kernel's t is 10^6 and its fp64 bias corrections come out of 20
+    squarings in pow_u64 (beta2^t underflows to 0, beta1^t long before it): the same bounds."""
+    agent = new_agent('leduc', lr=1e-3, adam='seeded')
+    for st in agent._adam_state()[1]:
+        st['step'].fill_(999999)
+    check_adam(agent, (10 ** 6,), 1e-3)
+
+
 # ---- 5. chunking and determinism -------------------------------------------------------------------------------------
-@pytest.mark.parametrize('name', ['leduc', 'odd', 'uno', 'mahjong'])
+@pytest.mark.parametrize('name', ['leduc', 'odd', 'uno', 'mahjong', 'nolimit', 'blackjack', 'limit'])
 def test_chunking_and_determinism(name):
     """8 steps in one launch, in 8 launches, and as 3 + 5 leave bit-identical parameters, buffers, Adam state, target
     network and losses (target copies at train_t 3 and 6 included); so do two fresh runs."""
